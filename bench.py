@@ -16,8 +16,15 @@ BERT-base (BASELINE.json config 5): ``--model bert_base --optimizer gns`` trains
 masked positions + NSP, AdamW) through S-SGD with the gradient-noise-scale
 monitor and reports sequences/s (and tokens/s in ``config``).
 
+A plain run sets up, warms up, times ``--steps`` steps and prints the result line.  ``--full``
+adds what takes work of its own after the timed steps: the replica checksum comparison (exit 4 when
+the replicas diverged), the per-bucket communication probe (``--comm-probe`` extra eager steps) and
+the RCCL version / watchdog counters, all under ``verify``.  ``--dump-outputs DIR`` writes what the
+last timed step returned and left behind (the losses, the updated parameters and buffers) as
+``DIR/<name>.npy`` so that two builds can be compared output for output.
+
 Usage:
-    python bench.py [--gpus 1] [--steps 20] [--warmup 5]
+    python bench.py [--gpus 1] [--steps 20] [--warmup 5] [--full] [--dump-outputs DIR]
     python bench.py --model bert_base --optimizer gns
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \\
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
@@ -244,6 +251,45 @@ def _replica_checksum(opt, model):
     return tot.cpu()
 
 
+DUMP_MAX_ELEMS = 4 << 20  # per array: 16 MiB of float32, every model's dump stays far below 64 MB
+
+
+def _dump_sample(flat):
+    """``flat`` (1-D tensor) as a float32 numpy array: all of it up to DUMP_MAX_ELEMS elements, else
+    the elements at DUMP_MAX_ELEMS sorted positions drawn once from a generator seeded by the
+    length alone -- the same positions in every run and every build."""
+    import torch
+
+    n = flat.numel()
+    if n > DUMP_MAX_ELEMS:
+        g = torch.Generator(device="cpu")
+        g.manual_seed(20240229 + n)
+        idx = torch.randint(0, n, (DUMP_MAX_ELEMS,), generator=g).sort().values
+        flat = flat.index_select(0, idx.to(flat.device))
+    return flat.detach().float().cpu().numpy()
+
+
+def _dump_outputs(path, losses, opt, model):
+    """``--dump-outputs``: what the last timed step returned and left behind.  ``loss``: the value
+    it returned; ``losses``: every timed step's; ``params``: the f32 parameters after its update
+    (the flat master where the optimizer keeps one, else model.parameters() in order); ``buffers``:
+    the model's buffers (BN running statistics) in order."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    space = getattr(opt, "space", None)
+    params = (space.flat_param.detach().reshape(-1) if space is not None
+              else torch.cat([p.detach().reshape(-1).float() for p in model.parameters()]))
+    bufs = [b.detach().reshape(-1).float() for b in model.buffers()]
+    out = {"loss": np.asarray(losses[-1:], dtype=np.float32), "losses": np.asarray(losses, dtype=np.float32),
+           "params": _dump_sample(params)}
+    if bufs:
+        out["buffers"] = _dump_sample(torch.cat(bufs))
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=None,
@@ -287,9 +333,16 @@ def main():
     p.add_argument("--emulate-ctas", type=int, default=16, help="--emulate-comm: workgroups per all-reduce")
     p.add_argument("--emulate-busbw", type=float, default=350.0, help="--emulate-comm: modelled ring busbw, GB/s")
     p.add_argument("--emulate-lat-us", type=float, default=25.0, help="--emulate-comm: modelled per-collective latency")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also compare the replicas' checksums (exit 4 when they diverged), run "
+                        "the --comm-probe steps and read the RCCL version / watchdog counters (all under verify)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write the last step's loss, every timed step's loss, the updated f32 "
+                        "parameters and the model's buffers (a fixed seeded sample of at most %d elements each) as "
+                        "DIR/<name>.npy (float32; rank 0)" % DUMP_MAX_ELEMS)
     p.add_argument("--comm-probe", type=int, default=3, metavar="STEPS",
-                   help="after the timed steps: this many extra (untimed, eager) steps with HIP events around every "
-                        "bucket collective -> verify.comm_per_bucket_ms / exposed_comm_ms (0 = off)")
+                   help="--full: after the timed steps, this many extra (untimed, eager) steps with HIP events around "
+                        "every bucket collective -> verify.comm_per_bucket_ms / exposed_comm_ms (0 = off)")
     p.add_argument("--elastic", default=None, metavar="SIZE:STEPS,...",
                    help="elastic run (config 5): resize the job along this schedule, e.g. 4:20,8:20 "
                         "(self-launches kungfu-run -w with its built-in config server)")
@@ -479,9 +532,11 @@ def main():
     dt_all = (kf.ops.all_gather(torch.tensor([dt], dtype=torch.float64)).view(-1).tolist() if size > 1 else [dt])
     dt_max = max(dt_all)
     value = a.batch * size * a.steps / dt_max
+    if a.dump_outputs and rank == 0:  # before the probe's extra steps move the parameters on
+        _dump_outputs(a.dump_outputs, loss_buf.tolist(), opt, model)
     reducer = getattr(opt, "reducer", None)
     comm_probe = None
-    if a.comm_probe > 0 and cuda and reducer is not None and not reducer.skip:
+    if a.full and a.comm_probe > 0 and cuda and reducer is not None and not reducer.skip:
         # untimed: where an N-rank step's communication goes, per bucket (HIP events, eager steps)
         reducer.probe = []
         for _ in range(a.comm_probe):
@@ -501,27 +556,29 @@ def main():
                      "comm_bytes_per_step": opt.space.numel * 4}
     else:
         comm_info = {"comm_ranks": size}
-    # replica consistency: after synchronous training every rank holds the same weights
-    ck = _replica_checksum(opt, model)
-    cks = kf.ops.all_gather(ck).view(size, 2) if size > 1 else ck.view(1, 2)
-    sync_algo = a.optimizer in ("ssgd", "gns")
-    consistent = bool((cks == cks[0:1]).all()) if sync_algo else None
-    try:
-        rccl_ver = kf.show_rccl_version()
-    except Exception:
-        rccl_ver = None
-    from kungfu_amd._lib import hip as _hip_mod
+    sync_algo = a.full and a.optimizer in ("ssgd", "gns")
+    cks, consistent, rccl_ver, wd = None, None, None, None
+    if a.full:
+        # replica consistency: after synchronous training every rank holds the same weights
+        ck = _replica_checksum(opt, model)
+        cks = kf.ops.all_gather(ck).view(size, 2) if size > 1 else ck.view(1, 2)
+        consistent = bool((cks == cks[0:1]).all()) if sync_algo else None
+        try:
+            rccl_ver = kf.show_rccl_version()
+        except Exception:
+            rccl_ver = None
+        from kungfu_amd._lib import hip as _hip_mod
 
-    try:
-        # every collective has completed (synchronised above); give the watchdog thread (50 ms
-        # poll period) a moment to retire their events before reading its counters
-        t_wd = time.time() + 2.0
-        wd = dict(_hip_mod().rccl_watchdog_info())
-        while wd["pending"] and time.time() < t_wd:
-            time.sleep(0.02)
+        try:
+            # every collective has completed (synchronised above); give the watchdog thread (50 ms
+            # poll period) a moment to retire their events before reading its counters
+            t_wd = time.time() + 2.0
             wd = dict(_hip_mod().rccl_watchdog_info())
-    except Exception:
-        wd = None
+            while wd["pending"] and time.time() < t_wd:
+                time.sleep(0.02)
+                wd = dict(_hip_mod().rccl_watchdog_info())
+        except Exception:
+            wd = None
     verify = {
         "launch": kf.launch_mode(),
         "world_size": size,
@@ -531,7 +588,7 @@ def main():
         "per_rank_img_s": {"min": round(a.batch * a.steps / max(dt_all), 2),
                            "max": round(a.batch * a.steps / min(dt_all), 2)},
         "replicas_consistent": consistent,
-        "replica_checksum": [float(x) for x in cks[0].tolist()],
+        "replica_checksum": [float(x) for x in cks[0].tolist()] if cks is not None else None,
         "rccl_watchdog": ({"ops_watched": wd["registered"], "pending": wd["pending"], "timeout_s": wd["timeout_s"],
                            "abort_on_stall": wd.get("abort_on_stall")} if wd else None),
         "rccl_ctas": list(getattr(getattr(reducer, "comm", None), "ctas", (0, 0)) or (0, 0)),
@@ -593,6 +650,7 @@ def main():
             "losses": losses,
             "comm": comm_info,
         },
+        "full": bool(a.full),
         "verify": verify,
     }
     if rank == 0:

@@ -33,7 +33,7 @@ def _bench(args, env=None, timeout=300):
 
 def test_bench_self_launches_and_verifies_replicas():
     r = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--device", "cpu", "--model", "resnet18",
-                "--batch", "2", "--image-size", "32"])
+                "--batch", "2", "--image-size", "32", "--full"])
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout  # rank 0 only

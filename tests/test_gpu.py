@@ -574,7 +574,7 @@ def test_bench_torchrun_two_ranks_one_gpu_host_staged():
     port = free_port_block(2)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "16"],
+                        "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "16", "--full"],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

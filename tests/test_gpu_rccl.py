@@ -53,7 +53,7 @@ def _bench(env, extra=(), expect_rc=0, gpus=2, batch=16, timeout=600):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "KUNGFU_SELF_SPEC"):
         e.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "3", "--warmup",
-                        "2", "--batch", str(batch)] + list(extra), cwd=ROOT, env=e, stdout=subprocess.PIPE,
+                        "2", "--batch", str(batch), "--full"] + list(extra), cwd=ROOT, env=e, stdout=subprocess.PIPE,
                        stderr=subprocess.STDOUT, text=True, timeout=timeout)
     if expect_rc != 0:
         assert r.returncode != 0, r.stdout[-5000:]
