@@ -297,64 +297,10 @@ at::Tensor conv3x3(at::Tensor x, at::Tensor w, int64_t stride, int64_t variant) 
 // input is bn_x; stats then receive sum(dz), sum(dz * x) (dz = grad * relu') for
 // bn_backward(..., sums=stats).  bn_mask (1 bit per element) or bn_fcoef (forward
 // [scale; shift]) gives the ReLU gate.
-// In-launch BN finalize descriptor (kfk::BNFin) packed on the host into a CPU uint8 tensor; the
-// caller keeps a device copy and passes it to conv / conv_dgrad_s2 as `fin`.  mode 1 (forward):
-//   t = [arrive(int32 >= 9, zeroed), gamma, beta, mean, invstd, coef(2C), running_mean, running_var, num_batches]
-// mode 2 (backward): t = [arrive, gamma, mean, invstd, coef(3C), dgamma, dbeta]; f32 per-channel tensors.
-at::Tensor bn_fin_desc(int64_t mode, std::vector<at::Tensor> v, int64_t rows, double momentum, double eps,
-                       bool training) {
-    TORCH_CHECK(mode == 1 || mode == 2, "bn_fin_desc: mode 1 (forward) or 2 (backward)");
-    TORCH_CHECK(v.size() == (mode == 1 ? 9u : 7u), "bn_fin_desc: wrong tensor count for the mode");
-    TORCH_CHECK(v[0].is_cuda() && v[0].scalar_type() == at::kInt && v[0].numel() >= 9 && v[0].is_contiguous(),
-                "bn_fin_desc: arrive must be a zeroed int32 GPU tensor of >= 9 words");
-    const int C = static_cast<int>(v[1].numel());
-    auto f32 = [&](const at::Tensor &a, int64_t n, const char *what) -> float * {
-        TORCH_CHECK(a.defined() && a.scalar_type() == at::kFloat && a.numel() == n && a.is_contiguous() &&
-                        a.device() == v[0].device(),
-                    "bn_fin_desc: ", what, " must be a contiguous f32 tensor of ", n, " elements on arrive's device");
-        return a.data_ptr<float>();
-    };
-    kfk::BNFin f;
-    f.mode = static_cast<int>(mode);
-    f.arrive = reinterpret_cast<unsigned *>(v[0].data_ptr<int>());
-    f.rows = rows;
-    f.training = training ? 1 : 0;
-    f.momentum = static_cast<float>(momentum), f.eps = static_cast<float>(eps);
-    f.gamma = f32(v[1], C, "gamma");
-    if (mode == 1) {
-        f.beta = f32(v[2], C, "beta");
-        f.mean = f32(v[3], C, "mean");
-        f.invstd = f32(v[4], C, "invstd");
-        f.coef = f32(v[5], 2 * C, "coef");
-        f.run_mean = f32(v[6], C, "running_mean");
-        f.run_var = f32(v[7], C, "running_var");
-        TORCH_CHECK(v[8].scalar_type() == at::kLong && v[8].numel() == 1, "bn_fin_desc: num_batches must be int64[1]");
-        f.num_batches = v[8].data_ptr<int64_t>();
-    } else {
-        f.mean = f32(v[2], C, "mean");
-        f.invstd = f32(v[3], C, "invstd");
-        f.coef = f32(v[4], 3 * C, "coef");
-        f.dgamma = f32(v[5], C, "dgamma");
-        f.dbeta = f32(v[6], C, "dbeta");
-    }
-    auto out = at::empty({static_cast<int64_t>(sizeof(kfk::BNFin))}, at::TensorOptions().dtype(at::kByte));
-    std::memcpy(out.data_ptr<uint8_t>(), &f, sizeof(f));
-    return out;
-}
-
-static const kfk::BNFin *fin_ptr(const c10::optional<at::Tensor> &fin, const at::Tensor &like, int C) {
-    if (!fin || !fin->defined()) return nullptr;
-    TORCH_CHECK(fin->is_cuda() && fin->device() == like.device() && fin->scalar_type() == at::kByte &&
-                    fin->numel() == static_cast<int64_t>(sizeof(kfk::BNFin)) && fin->is_contiguous(),
-                "fin: must be the device copy of a bn_fin_desc descriptor on the conv's device");
-    return reinterpret_cast<const kfk::BNFin *>(fin->data_ptr<uint8_t>());
-}
-
 at::Tensor conv(at::Tensor x, at::Tensor w, int64_t stride, c10::optional<at::Tensor> stats,
                 c10::optional<at::Tensor> out, int64_t variant, c10::optional<at::Tensor> bn_x,
                 c10::optional<at::Tensor> bn_fcoef, c10::optional<at::Tensor> bn_mask,
-                c10::optional<at::Tensor> bias, bool gate, c10::optional<at::Tensor> acc_mask, bool acc_even,
-                c10::optional<at::Tensor> fin) {
+                c10::optional<at::Tensor> bias, bool gate, c10::optional<at::Tensor> acc_mask, bool acc_even) {
     TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 4 &&
                     x.is_contiguous(at::MemoryFormat::ChannelsLast),
                 "conv: x must be a 4-D channels_last bf16 GPU tensor");
@@ -447,9 +393,6 @@ at::Tensor conv(at::Tensor x, at::Tensor w, int64_t stride, c10::optional<at::Te
                     "conv: acc_even needs out, stride 1 and no acc_mask / bn_fcoef");
         epi |= kfk::kEpiAccEven;
     }
-    ea.fin = fin_ptr(fin, x, K);
-    TORCH_CHECK(!ea.fin || (epi & (kfk::kEpiFwdStats | kfk::kEpiBwdCoef | kfk::kEpiBwdBits)),
-                "conv: fin needs the statistics epilogue (stats) or the BN-backward sums (stats + bn_x)");
     kfk::launch_conv(reinterpret_cast<const uint16_t *>(x.data_ptr()), reinterpret_cast<const uint16_t *>(w.data_ptr()),
                      reinterpret_cast<uint16_t *>(y.data_ptr()), N, H, W, C, K, ks, static_cast<int>(stride), ea, epi,
                      stream_of(x, 0), static_cast<int>(variant));
@@ -521,8 +464,7 @@ std::vector<at::Tensor> gemm(at::Tensor x, at::Tensor w, c10::optional<at::Tenso
 // gradient conv(..., out=dx, acc_even=True).
 at::Tensor conv_dgrad_s2(at::Tensor dy, at::Tensor wt, int64_t ks, c10::optional<at::Tensor> stats,
                          c10::optional<at::Tensor> bn_x, c10::optional<at::Tensor> bn_fcoef,
-                         c10::optional<at::Tensor> bn_mask, int64_t variant, int64_t dh, int64_t dw, int64_t pad,
-                         c10::optional<at::Tensor> fin) {
+                         c10::optional<at::Tensor> bn_mask, int64_t variant, int64_t dh, int64_t dw, int64_t pad) {
     TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == at::kBFloat16 && dy.dim() == 4 &&
                     dy.is_contiguous(at::MemoryFormat::ChannelsLast),
                 "conv_dgrad_s2: dy must be a 4-D channels_last bf16 GPU tensor");
@@ -571,8 +513,6 @@ at::Tensor conv_dgrad_s2(at::Tensor dy, at::Tensor wt, int64_t ks, c10::optional
             epi = kfk::kEpiBwdCoef;
         }
     }
-    ea.fin = fin_ptr(fin, dy, C);
-    TORCH_CHECK(!ea.fin || epi != 0, "conv_dgrad_s2: fin needs the BN-backward sums (stats + bn_x)");
     kfk::launch_conv_dgrad_s2(reinterpret_cast<const uint16_t *>(dy.data_ptr()),
                               reinterpret_cast<const uint16_t *>(wt.data_ptr()), reinterpret_cast<uint16_t *>(dx.data_ptr()),
                               N, OH, OW, K, C, static_cast<int>(ks), ea, epi, stream_of(dy, 0),
@@ -1255,7 +1195,7 @@ std::vector<at::Tensor> bn_forward(at::Tensor x, c10::optional<at::Tensor> res, 
     at::Tensor mean, invstd, coef;
     const bool prefin = pre.has_value();
     if (prefin) {
-        // (mean, invstd, coef) already written from `sums` by the producing conv's in-launch finalize
+        // (mean, invstd, coef) already written from `sums` by the batched bn_finalize_multi launch
         TORCH_CHECK(pre->size() == 3 && training && sums && sums->defined(), "bn: pre = (mean, invstd, coef) with sums");
         mean = (*pre)[0], invstd = (*pre)[1], coef = (*pre)[2];
         TORCH_CHECK(mean.scalar_type() == at::kFloat && mean.numel() == C && invstd.numel() == C &&
@@ -1289,8 +1229,7 @@ std::vector<at::Tensor> bn_forward(at::Tensor x, c10::optional<at::Tensor> res, 
 std::vector<at::Tensor> bn_backward(at::Tensor dy, at::Tensor x, at::Tensor mean, at::Tensor invstd,
                                     at::Tensor weight, at::Tensor fcoef, c10::optional<at::Tensor> mask, bool relu,
                                     bool training, bool want_dres, c10::optional<at::Tensor> sums,
-                                    c10::optional<at::Tensor> dres_x, c10::optional<at::Tensor> dres_sums,
-                                    c10::optional<std::vector<at::Tensor>> pre) {
+                                    c10::optional<at::Tensor> dres_x, c10::optional<at::Tensor> dres_sums) {
     auto sh = bn_shape(x);
     const int C = sh.channels;
     // dy may be a channel slice of a wider channels-last tensor (a concatenation's gradient):
@@ -1316,17 +1255,7 @@ std::vector<at::Tensor> bn_backward(at::Tensor dy, at::Tensor x, at::Tensor mean
     auto dx = at::empty_like(x, at::MemoryFormat::ChannelsLast);
     at::Tensor dres;
     if (want_dres) dres = at::empty_like(x, at::MemoryFormat::ChannelsLast);
-    at::Tensor dw, db, coef;
-    const bool prefin = pre.has_value();
-    if (prefin) {
-        // (dgamma, dbeta, coef) already written from `sums` by the dgrad conv's in-launch finalize
-        TORCH_CHECK(pre->size() == 3 && sums && sums->defined(), "bn_backward: pre = (dgamma, dbeta, coef) with sums");
-        dw = (*pre)[0], db = (*pre)[1], coef = (*pre)[2];
-        TORCH_CHECK(dw.scalar_type() == at::kFloat && dw.numel() == C && db.numel() == C && coef.numel() == 3 * C,
-                    "bn_backward: pre tensors must be f32 dgamma[C], dbeta[C], coef[3C]");
-    } else {
-        dw = at::empty({C}, fopt), db = at::empty({C}, fopt), coef = at::empty({3 * C}, fopt);
-    }
+    at::Tensor dw = at::empty({C}, fopt), db = at::empty({C}, fopt), coef = at::empty({3 * C}, fopt);
     double *sp = nullptr;
     if (sums && sums->defined()) {
         TORCH_CHECK(sums->is_cuda() && sums->scalar_type() == at::kDouble && sums->numel() == 2 * C * kfk::kStatSlots &&
@@ -1352,7 +1281,7 @@ std::vector<at::Tensor> bn_backward(at::Tensor dy, at::Tensor x, at::Tensor mean
                             training, partial.defined() ? partial.data_ptr<float>() : nullptr, dw.data_ptr<float>(),
                             db.data_ptr<float>(), coef.data_ptr<float>(), reinterpret_cast<uint16_t *>(dx.data_ptr()),
                             want_dres ? reinterpret_cast<uint16_t *>(dres.data_ptr()) : nullptr, stream_of(x, 0), sp,
-                            dsx, dsp, dy_ld, prefin);
+                            dsx, dsp, dy_ld);
     return {dx, dres, dw, db};
 }
 
@@ -1417,7 +1346,7 @@ std::vector<std::vector<at::Tensor>> bn_backward_multi(std::vector<at::Tensor> d
                                     weights[i].data_ptr<float>(), p.sh, true, true, p.partial.data_ptr<float>(),
                                     p.dw.data_ptr<float>(), p.db.data_ptr<float>(), p.coef.data_ptr<float>(),
                                     reinterpret_cast<uint16_t *>(p.dx.data_ptr()), nullptr, st, nullptr, nullptr,
-                                    nullptr, p.ld, false, phase);
+                                    nullptr, p.ld, phase);
         }
     }
     std::vector<std::vector<at::Tensor>> out;
@@ -2055,8 +1984,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "accumulate epilogues", py::arg("x"), py::arg("w"), py::arg("stride") = 1, py::arg("stats") = py::none(),
           py::arg("out") = py::none(), py::arg("variant") = -1, py::arg("bn_x") = py::none(),
           py::arg("bn_fcoef") = py::none(), py::arg("bn_mask") = py::none(), py::arg("bias") = py::none(),
-          py::arg("gate") = false, py::arg("acc_mask") = py::none(), py::arg("acc_even") = false,
-          py::arg("fin") = py::none());
+          py::arg("gate") = false, py::arg("acc_mask") = py::none(), py::arg("acc_even") = false);
     m.def("stem3_pack_weight", &stem3_pack_weight, "pack [32, 3, KH, KW] stem weights for stem3_forward");
     m.def("stem3_forward", &stem3_forward, "small image-stem conv (<= 4x4 window, 3 -> 32 channels) with the BN-sums "
           "epilogue", py::arg("x"), py::arg("wp"), py::arg("kh"), py::arg("kw"), py::arg("stride"), py::arg("ph"),
@@ -2064,9 +1992,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("stem3_wgrad", &stem3_wgrad, "its weight gradient (MFMA over pixels, deterministic)", py::arg("dy"),
           py::arg("x"), py::arg("kh"), py::arg("kw"), py::arg("stride"), py::arg("ph"), py::arg("pw"),
           py::arg("out_f32") = false);
-    m.def("bn_fin_desc", &bn_fin_desc, "pack an in-launch BN finalize descriptor (CPU uint8; copy it to the GPU)",
-          py::arg("mode"), py::arg("tensors"), py::arg("rows"), py::arg("momentum") = 0.1, py::arg("eps") = 1e-5,
-          py::arg("training") = true);
     m.def("conv_rect", &conv_rect, "KH x KW NHWC bf16 convolution with zero padding (MFMA implicit GEMM; "
           "Inception-v3 windows) with an optional BN-statistics epilogue", py::arg("x"), py::arg("w"),
           py::arg("stride") = 1, py::arg("ph") = 0, py::arg("pw") = 0, py::arg("stats") = py::none(),
@@ -2080,8 +2005,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("conv_dgrad_s2", &conv_dgrad_s2, "data gradient of a stride-2 1x1/3x3 NHWC bf16 convolution (parity-phase "
           "MFMA implicit GEMMs)", py::arg("dy"), py::arg("wt"), py::arg("ks"), py::arg("stats") = py::none(),
           py::arg("bn_x") = py::none(), py::arg("bn_fcoef") = py::none(), py::arg("bn_mask") = py::none(),
-          py::arg("variant") = -1, py::arg("dh") = 0, py::arg("dw") = 0, py::arg("pad") = 1,
-          py::arg("fin") = py::none());
+          py::arg("variant") = -1, py::arg("dh") = 0, py::arg("dw") = 0, py::arg("pad") = 1);
     m.def("xent_forward", &xent_forward, "fused softmax cross-entropy over bf16 logits: (lse, per-row loss)");
     m.def("xent_backward", &xent_backward, "its bf16 logit gradient, scaled by scale[0]");
     m.def("gelu_backward_colsum", &gelu_backward_colsum, "erf-GELU backward du and the column sums of du",
@@ -2158,7 +2082,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("bn_backward", &bn_backward, "fused NHWC BN(+residual)(+ReLU) backward -> (dx, dres, dweight, dbias)",
           py::arg("dy"), py::arg("x"), py::arg("mean"), py::arg("invstd"), py::arg("weight"), py::arg("fcoef"),
           py::arg("mask"), py::arg("relu"), py::arg("training"), py::arg("want_dres"), py::arg("sums") = py::none(),
-          py::arg("dres_x") = py::none(), py::arg("dres_sums") = py::none(), py::arg("pre") = py::none());
+          py::arg("dres_x") = py::none(), py::arg("dres_sums") = py::none());
     m.def("bn_pool_supported", [](int64_t C, int64_t H, int64_t W) {
         return kfk::bn_pool_supported(kfk::BNShape{H * W, static_cast<int>(C)}, static_cast<int>(H),
                                       static_cast<int>(W));

@@ -83,14 +83,8 @@ __device__ __forceinline__ void st16(uint4 *p, const uint4 &v, bool nt) {
 
 // default 1 (non-temporal loads): ResNet-50 step 21.73 -> 21.39 ms on MI355X, while
 // non-temporal stores did not pay in the full step (profiles/README.md, r3f)
-// (the round-3 timing experiment that skipped the sums-finalize launches -- an upper bound of
-// 1.0 ms/step on what folding them elsewhere could save -- is retired with its knob, round 5)
-bool bn_skip_finalize() { return false; }
-
 // non-temporal loads, plain stores (bit 0 loads, bit 1 stores; the round-3 A/B above)
 int bn_nt_mode() { return 1; }
-
-int bn_max_grid(int def) { return def; }
 
 struct Chunking {
     int64_t rows_per_chunk;
@@ -916,8 +910,7 @@ void dispatch_cvec(int cvec, F &&f) {
 int apply_grid(int64_t nvec, int cvec) {
     const int nt = (kBlock / cvec) * cvec;
     int64_t g = (nvec + nt - 1) / nt;
-    const int mg = bn_max_grid(kMaxGrid);
-    if (g > mg) g = mg;
+    if (g > kMaxGrid) g = kMaxGrid;
     if (g < 1) g = 1;
     return static_cast<int>(g);
 }
@@ -942,7 +935,7 @@ void launch_backward_impl(G grad, const uint16_t *x, const float *fcoef, const u
                           const float *invstd, const float *gamma, BNShape sh, int rm, bool training, float *partial,
                           float *dgamma, float *dbeta, float *coef, uint16_t *dx, uint16_t *dres, hipStream_t s,
                           double *sums = nullptr, const uint16_t *dres_x = nullptr, double *dres_sums = nullptr,
-                          bool prefinalized = false, int phase = 0) {
+                          int phase = 0) {
     // phase 0: everything; 1: the reduce pass only (statistics path, no sums); 2: the apply pass only
     // (coef already finalized -- bn_bwd_finalize_multi); 3: statistics + finalize, no apply (the
     // caller consumes coef itself: the stem's fused weight gradient)
@@ -952,7 +945,6 @@ void launch_backward_impl(G grad, const uint16_t *x, const float *fcoef, const u
     const uint4 *xx = reinterpret_cast<const uint4 *>(x);
     if (phase == 2) {
     } else if (sums) {
-        if (!prefinalized && !bn_skip_finalize())
         bn_bwd_finalize_sums<<<(C + 255) / 256, 256, 0, s>>>(sums, C, sh.rows, gamma, mean, invstd, dgamma, dbeta,
                                                              coef, training);
     } else {
@@ -1014,7 +1006,6 @@ void launch_bn_sums_finalize_multi(const BnFinBatch &b, hipStream_t s) {
     if (b.n > kBnFinMax) throw std::invalid_argument("bn_sums_finalize_multi: too many BNs");
     int cmax = 0;
     for (int i = 0; i < b.n; ++i) cmax = b.d[i].C > cmax ? b.d[i].C : cmax;
-    if (bn_skip_finalize()) return;
     bn_sums_finalize_multi<<<dim3((cmax + 255) / 256, b.n), 256, 0, s>>>(b);
 }
 
@@ -1041,9 +1032,9 @@ void launch_bn_forward(const uint16_t *x, const uint16_t *res, const float *gamm
         throw std::invalid_argument("bn_forward: a strided output needs BN+ReLU without residual, row stride % 8");
     const int64_t nvec = sh.rows * cvec;
     if (training && sums) {
-        if (!prefinalized && !bn_skip_finalize())
-        bn_sums_finalize<<<(C + 255) / 256, 256, 0, s>>>(sums, C, sh.rows, gamma, beta, mean, invstd, run_mean,
-                                                         run_var, momentum, eps, coef, num_batches);
+        if (!prefinalized)
+            bn_sums_finalize<<<(C + 255) / 256, 256, 0, s>>>(sums, C, sh.rows, gamma, beta, mean, invstd, run_mean,
+                                                             run_var, momentum, eps, coef, num_batches);
     } else if (training) {
         launch_stats(x, sh, gamma, beta, run_mean, run_var, momentum, eps, partial, mean, invstd, coef, num_batches,
                      s);
@@ -1079,17 +1070,17 @@ void launch_bn_backward(const uint16_t *dy, const uint16_t *x, const float *fcoe
                         const float *mean, const float *invstd, const float *gamma, BNShape sh, bool relu,
                         bool training, float *partial, float *dgamma, float *dbeta, float *coef, uint16_t *dx,
                         uint16_t *dres, hipStream_t s, double *sums, const uint16_t *dres_x, double *dres_sums,
-                        int64_t dy_ld, bool prefinalized, int phase) {
+                        int64_t dy_ld, int phase) {
     const int rm = !relu ? RM_NONE : (mask ? RM_BITS : RM_COEF);
     if (dy_ld > 0 && dy_ld != sh.channels) {
         if (dy_ld % 8) throw std::invalid_argument("bn_backward: dy row stride must be a multiple of 8");
         launch_backward_impl(StridedGrad{reinterpret_cast<const uint4 *>(dy), dy_ld / 8}, x, fcoef, mask, mean, invstd,
                              gamma, sh, rm, training, partial, dgamma, dbeta, coef, dx, dres, s, sums, dres_x,
-                             dres_sums, prefinalized, phase);
+                             dres_sums, phase);
         return;
     }
     launch_backward_impl(DirectGrad{reinterpret_cast<const uint4 *>(dy), (bn_nt_mode() & 1) != 0}, x, fcoef, mask, mean, invstd, gamma, sh, rm,
-                         training, partial, dgamma, dbeta, coef, dx, dres, s, sums, dres_x, dres_sums, prefinalized, phase);
+                         training, partial, dgamma, dbeta, coef, dx, dres, s, sums, dres_x, dres_sums, phase);
 }
 
 bool bn_pool_supported(BNShape sh, int H, int W) {
@@ -1103,7 +1094,6 @@ void launch_bn_pool_forward(const uint16_t *x, const float *gamma, const float *
                             hipStream_t s, double *sums, uint16_t *xarg) {
     const int C = sh.channels, cvec = C / 8;
     if (training && sums) {
-        if (!bn_skip_finalize())
         bn_sums_finalize<<<(C + 255) / 256, 256, 0, s>>>(sums, C, sh.rows, gamma, beta, mean, invstd, run_mean,
                                                          run_var, momentum, eps, coef, num_batches);
     } else if (training) {
@@ -1147,7 +1137,7 @@ void launch_bn_pool_backward(const uint16_t *dyp, const uint8_t *arg, const uint
     PoolGrad pg{reinterpret_cast<const uint4 *>(dyp), reinterpret_cast<const uint2 *>(arg), H, W, pool_out(H),
                 pool_out(W), m_hw, m_w};
     launch_backward_impl(pg, x, fcoef, nullptr, mean, invstd, gamma, sh, RM_COEF, training, partial, dgamma, dbeta,
-                         coef, dx, nullptr, s, sums, nullptr, nullptr, false, apply ? 0 : 3);
+                         coef, dx, nullptr, s, sums, nullptr, nullptr, apply ? 0 : 3);
 }
 
 }  // namespace kfk

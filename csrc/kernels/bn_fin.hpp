@@ -1,8 +1,7 @@
-// BN finalize math shared by the standalone finalize kernels (bn.hip) and the in-kernel
-// finalize of the convolution's statistics epilogues (conv.hip): per channel, from the f64 sums
-// of the kStatSlots slots, the forward batch statistics / affine coefficients / running stats,
-// or the backward dgamma / dbeta and the three backward-apply coefficients.  One definition,
-// so both paths produce bit-identical results.
+// BN finalize math of the finalize kernels (bn.hip, its only users): per channel, from the f64
+// sums of the kStatSlots slots, the forward batch statistics / affine coefficients / running
+// stats, or the backward dgamma / dbeta and the three backward-apply coefficients.  One
+// definition, so the single and the batched finalize kernels produce bit-identical results.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -54,22 +53,6 @@ __device__ __forceinline__ void bn_fin_bwd_channel(int c, int C, double s0, doub
         coef[C + c] = 0.f;
         coef[2 * C + c] = 0.f;
     }
-}
-
-// pointer forms (the in-launch finalize of conv.hip): the loads behind the caller's own
-__device__ __forceinline__ void bn_fin_fwd_channel_p(int c, int C, double s, double q, int64_t rows,
-                                                     const float *gamma, const float *beta, float *mean,
-                                                     float *invstd, float *run_mean, float *run_var, float momentum,
-                                                     float eps, float *coef) {
-    bn_fin_fwd_channel(c, C, s, q, rows, gamma ? gamma[c] : 1.f, beta ? beta[c] : 0.f, run_mean ? run_mean[c] : 0.f,
-                       run_mean ? run_var[c] : 0.f, mean, invstd, run_mean, run_var, momentum, eps, coef);
-}
-
-__device__ __forceinline__ void bn_fin_bwd_channel_p(int c, int C, double s0, double s1, int64_t rows,
-                                                     const float *gamma, const float *mean, const float *invstd,
-                                                     float *dgamma, float *dbeta, float *coef, bool training) {
-    bn_fin_bwd_channel(c, C, s0, s1, rows, gamma ? gamma[c] : 1.f, mean[c], invstd[c], dgamma, dbeta, coef,
-                       training);
 }
 
 }  // namespace kfk

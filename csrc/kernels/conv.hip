@@ -8,13 +8,14 @@
 // Why: ResNet-50 spends ~6.3 ms of a 28.6 ms step in its 16 3x3 convolutions at
 // ~450 TF/s through MIOpen/CK (profiles/README.md).  The K dimension of one
 // tap is a run of Cin contiguous channels, so every A-tile row is a 128-byte
-// segment of the input (or of a zero page at the padding border): the im2col
-// is done by the per-lane source address of global_load_lds, never in memory.
+// segment of the input (or zeros at the padding border: an out-of-range buffer
+// offset): the im2col is done by the per-lane source offset of the LDS-DMA
+// buffer load, never in memory.
 //
 // Tiling: block = 4 waves (256 threads), wave tile 64x64 (4x4 MFMA 16x16
 // tiles, 64 accumulator VGPRs), block tile 128x128 (2x2 waves) or 256x64 (4x1,
 // for Cout = 64), BK = 64 channels of one tap per K-step.  A and B tiles are
-// staged global->LDS with 16-byte global_load_lds (no VGPR round trip),
+// staged global->LDS with 16-byte LDS-DMA buffer loads (no VGPR round trip),
 // double-buffered, with an XOR swizzle of the 16-byte chunk index by the row
 // (chunk ^ (row & 7)) applied on the source address and on the ds_read, so the
 // 16 rows a ds_read_b128 touches spread over 8 chunk positions.  Blocks are
@@ -131,7 +132,8 @@ int conv_stagger() { return 1; }
 // static s_setprio 1 for the upper wave half of the 8-wave tiles: measured neutral (r3), off
 int conv_prio() { return 0; }
 
-// 256-byte zero page for padding rows (global_load_lds needs a real address).
+// 256-byte zero page for the weight-gradient kernels' padding rows (conv_wgrad.hip: global_load_lds
+// needs a real address).
 const void *zero_page() {
     static void *p = [] {
         void *q = nullptr;
@@ -144,8 +146,8 @@ const void *zero_page() {
 
 // Buffer-resource staging addresses x and w with 32-bit byte offsets below kBufOOB.
 void check_buf_extent(const Geo &g) {
-    if (KUNGFU_CONV_BUFLD && (static_cast<int64_t>(g.N) * g.H * g.W * g.C * 2 >= kBufOOB ||
-                              static_cast<int64_t>(g.K) * (g.wtaps > 0 ? g.wtaps : 1) * g.C * 2 >= kBufOOB))
+    if (static_cast<int64_t>(g.N) * g.H * g.W * g.C * 2 >= kBufOOB ||
+        static_cast<int64_t>(g.K) * (g.wtaps > 0 ? g.wtaps : 1) * g.C * 2 >= kBufOOB)
         throw std::invalid_argument("conv: input or weight of 2 GiB or more (buffer-resource staging)");
 }
 

@@ -17,14 +17,11 @@ void launch_gemm_t(const uint16_t *x, const uint16_t *w, uint16_t *y, Geo g, con
     g.ntiles = g.K / BN;
     check_buf_extent(g);
     const dim3 grid(g.mtiles * g.ntiles), block(64 * WM * WN);
-    const uint16_t *z = reinterpret_cast<const uint16_t *>(zero_page());
     switch (epi) {
-    case 0: conv_kernel<1, WM, WN, ST, 0, TM, TN><<<grid, block, 0, s>>>(x, w, y, z, g, ea); break;
-    case kEpiBias: conv_kernel<1, WM, WN, ST, kEpiBias, TM, TN><<<grid, block, 0, s>>>(x, w, y, z, g, ea); break;
-    case kEpiGeluGrad:
-        conv_kernel<1, WM, WN, ST, kEpiGeluGrad, TM, TN><<<grid, block, 0, s>>>(x, w, y, z, g, ea);
-        break;
-    case kEpiAccum: conv_kernel<1, WM, WN, ST, kEpiAccum, TM, TN><<<grid, block, 0, s>>>(x, w, y, z, g, ea); break;
+    case 0: conv_kernel<1, WM, WN, ST, 0, TM, TN><<<grid, block, 0, s>>>(x, w, y, g, ea); break;
+    case kEpiBias: conv_kernel<1, WM, WN, ST, kEpiBias, TM, TN><<<grid, block, 0, s>>>(x, w, y, g, ea); break;
+    case kEpiGeluGrad: conv_kernel<1, WM, WN, ST, kEpiGeluGrad, TM, TN><<<grid, block, 0, s>>>(x, w, y, g, ea); break;
+    case kEpiAccum: conv_kernel<1, WM, WN, ST, kEpiAccum, TM, TN><<<grid, block, 0, s>>>(x, w, y, g, ea); break;
     default: throw std::invalid_argument("gemm: unsupported epilogue");
     }
 }

@@ -8,13 +8,14 @@
 // Why: ResNet-50 spends ~6.3 ms of a 28.6 ms step in its 16 3x3 convolutions at
 // ~450 TF/s through MIOpen/CK (profiles/README.md).  The K dimension of one
 // tap is a run of Cin contiguous channels, so every A-tile row is a 128-byte
-// segment of the input (or of a zero page at the padding border): the im2col
-// is done by the per-lane source address of global_load_lds, never in memory.
+// segment of the input (or zeros at the padding border: an out-of-range buffer
+// offset): the im2col is done by the per-lane source offset of the LDS-DMA
+// buffer load, never in memory.
 //
 // Tiling: block = 4 waves (256 threads), wave tile 64x64 (4x4 MFMA 16x16
 // tiles, 64 accumulator VGPRs), block tile 128x128 (2x2 waves) or 256x64 (4x1,
 // for Cout = 64), BK = 64 channels of one tap per K-step.  A and B tiles are
-// staged global->LDS with 16-byte global_load_lds (no VGPR round trip),
+// staged global->LDS with 16-byte LDS-DMA buffer loads (no VGPR round trip),
 // double-buffered, with an XOR swizzle of the 16-byte chunk index by the row
 // (chunk ^ (row & 7)) applied on the source address and on the ds_read, so the
 // 16 rows a ds_read_b128 touches spread over 8 chunk positions.  Blocks are
@@ -28,7 +29,6 @@
 // conv_gemm.hip and conv_s2.hip, so the ~480 kernel instances build in parallel.
 #pragma once
 
-#include "bn_fin.hpp"
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -53,7 +53,6 @@ struct Geo {
     int prio;     // 1: the upper (second-dispatched) wave half runs at s_setprio 1
 };
 
-const void *zero_page();
 void check_buf_extent(const Geo &g);
 int conv_tile_rules();
 int conv_t224();
@@ -97,11 +96,8 @@ __device__ __forceinline__ void wait_vmcnt() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// Buffer-resource LDS-DMA staging in conv_kernel (KUNGFU_CONV_BUFLD): num_records = 2 GiB, so
+// Buffer-resource LDS-DMA staging in conv_kernel / conv_rows_kernel: num_records = 2 GiB, so
 // the out-of-range offset kBufOOB returns zeros; dword 3 = the CDNA raw-buffer format word.
-#ifndef KUNGFU_CONV_BUFLD
-#define KUNGFU_CONV_BUFLD 1
-#endif
 constexpr uint32_t kBufOOB = 0x80000000u;
 constexpr int kBufFlags = 0x00020000;
 
@@ -109,101 +105,29 @@ __device__ __forceinline__ __attribute__((address_space(3))) void *lds_ptr(uint8
     return (__attribute__((address_space(3))) void *)(p);
 }
 
-// In-launch BN finalize (kernels.hpp BNFin): called by every workgroup after its slot atomics.
-// Completion-ordered hand-off (MI355X_MICROARCH.md, inter-workgroup visibility: "the workgroup whose
-// add came last, told by the value its add returned", sc1 loads of the handed-off words): each wave
-// waits for its own atomics (vmcnt counts them), the workgroup joins a barrier, one lane arrives on
-// its shard counter (blockIdx % 8) and the last arriver of a shard on the top counter; the last of
-// those folds every channel's slots with sc1 loads (the f64 adds were performed at the memory side,
-// no L2 holds them) and re-zeroes slots and counters with sc1 stores for the next launch.  No fence:
-// the outputs are read by later kernels only.
-// `red` (the kernel's own LDS, free once the statistics are out) holds red_doubles doubles and then
-// the flag word: a separate __shared__ variable would push the 256x64 tiles' 80 KB past the
-// two-workgroups-per-CU LDS budget.
-__device__ __forceinline__ void bn_finalize_last(const BNFin *__restrict__ fp, double *sums, int C, int nwg, int orig,
-                                                 int tid, int nt, double *red, int red_doubles) {
-    int &s_last = *reinterpret_cast<int *>(red + red_doubles);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        const int shard = orig & 7;
-        const int nsh = nwg < 8 ? nwg : 8;
-        const unsigned nin = static_cast<unsigned>((nwg - shard + 7) / 8);
-        int last = 0;
-        unsigned *arrive = fp->arrive;
-        const unsigned o = __hip_atomic_fetch_add(arrive + shard, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (o == nin - 1) {
-            const unsigned o2 = __hip_atomic_fetch_add(arrive + 8, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            last = o2 == static_cast<unsigned>(nsh - 1);
-        }
-        s_last = last;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    // channel chunks staged through LDS (the main loop's buffers are free): every slot word of the
-    // chunk loaded once (sc1, all independent) and re-zeroed, then each channel folded in slot order
-    // k = 0..15 -- the order of bn_sums_finalize / bn_bwd_finalize_sums, so bit-identical to them
-    constexpr int KS2 = 2 * kStatSlots;
-    const int chunk = red_doubles / KS2 < C ? red_doubles / KS2 : C;
-    for (int c0 = 0; c0 < C; c0 += chunk) {
-        const int ch = C - c0 < chunk ? C - c0 : chunk;
-        const int items = KS2 * ch;
-#pragma unroll 8
-        for (int it = tid; it < items; it += nt) {
-            const int kw = it / ch, cc = it - kw * ch;  // kw = 2 k + which
-            double *a = sums + static_cast<int64_t>(kw) * C + c0 + cc;
-            red[it] = __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(a, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-        for (int cc = tid; cc < ch; cc += nt) {
-            double s0 = 0, s1 = 0;
-            for (int k = 0; k < kStatSlots; ++k) {
-                s0 += red[(2 * k) * ch + cc];
-                s1 += red[(2 * k + 1) * ch + cc];
-            }
-            const int c = c0 + cc;
-            if (fp->mode == 1)
-                bn_fin_fwd_channel_p(c, C, s0, s1, fp->rows, fp->gamma, fp->beta, fp->mean, fp->invstd, fp->run_mean,
-                                   fp->run_var, fp->momentum, fp->eps, fp->coef);
-            else
-                bn_fin_bwd_channel_p(c, C, s0, s1, fp->rows, fp->gamma, fp->mean, fp->invstd, fp->dgamma, fp->dbeta,
-                                   fp->coef, fp->training != 0);
-        }
-        __syncthreads();
-    }
-    if (tid < 9) __hip_atomic_store(fp->arrive + tid, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tid == 0 && fp->mode == 1 && fp->num_batches) fp->num_batches[0] += 1;
-}
-
-// The same finalize as a launch of its own (a non-persistent statistics launch: there every
-// workgroup would hold its CU through the wait for its atomics).
-__global__ void bn_fin_desc_kernel(const BNFin *__restrict__ fp, double *sums, int C) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    double v0[kStatSlots], v1[kStatSlots];
-#pragma unroll
-    for (int k = 0; k < kStatSlots; ++k) {
-        v0[k] = sums[k * 2 * C + c];
-        v1[k] = sums[k * 2 * C + C + c];
-    }
-    double s0 = 0, s1 = 0;
-#pragma unroll
-    for (int k = 0; k < kStatSlots; ++k) {
-        s0 += v0[k];
-        s1 += v1[k];
-        sums[k * 2 * C + c] = 0.0;
-        sums[k * 2 * C + C + c] = 0.0;
-    }
-    if (fp->mode == 1) {
-        if (c == 0 && fp->num_batches) fp->num_batches[0] += 1;
-        bn_fin_fwd_channel_p(c, C, s0, s1, fp->rows, fp->gamma, fp->beta, fp->mean, fp->invstd, fp->run_mean,
-                           fp->run_var, fp->momentum, fp->eps, fp->coef);
-    } else {
-        bn_fin_bwd_channel_p(c, C, s0, s1, fp->rows, fp->gamma, fp->mean, fp->invstd, fp->dgamma, fp->dbeta, fp->coef,
-                           fp->training != 0);
-    }
-}
+// Tile and epilogue constants of one (waves, wave tile, epilogue) combination, shared by conv_kernel,
+// conv_rows_kernel and the epilogue helpers below.
+template <int WM, int WN, int TM, int TN, int EPI>
+struct EpiTile {
+    // wave tile (16*TM) x (16*TN): TM x TN accumulators of one 16x16x32 MFMA each
+    static constexpr int WTM = 16 * TM, WTN = 16 * TN;
+    static constexpr int BM = WTM * WM, BN = WTN * WN, NT = 64 * WM * WN;
+    static constexpr int CROW = BN * 2 + 16;  // padded bytes per C row of the epilogue tile
+    static constexpr bool STATS = (EPI & (kEpiFwdStats | kEpiBwdCoef | kEpiBwdBits | kEpiGate | kEpiGeluGrad)) != 0;
+    static constexpr bool GATE = (EPI & kEpiGate) != 0;
+    static constexpr bool GELUG = (EPI & kEpiGeluGrad) != 0;
+    static constexpr bool BIAS = (EPI & (kEpiBiasRelu | kEpiBias)) != 0;
+    static constexpr int NSUM = (GATE || GELUG) ? 1 : 2;  // the gates need sum(y) only (a bias gradient)
+    static constexpr int VPR = BN / 8;  // 16-byte vectors per C row
+    static constexpr int GROUPS = NT / VPR;
+    static constexpr int ITER = BM * VPR / NT;  // 16-byte output vectors per thread per tile
+    static_assert(ITER * NT == BM * VPR, "whole store iterations");
+    static constexpr bool LD_OLD = (EPI & kEpiAccum) != 0;
+    static constexpr bool LD_BX = GATE || GELUG || (EPI & (kEpiBwdCoef | kEpiBwdBits)) != 0;
+    // the statistics reduction reuses the C tile's LDS once the last tile is stored
+    static constexpr int RED_BYTES = STATS ? NSUM * GROUPS * BN * 4 : 0;
+    static constexpr int EPI_BYTES = BM * CROW > RED_BYTES ? BM * CROW : RED_BYTES;
+};
 
 // The epilogue of one output tile (shared by conv_kernel and conv_rows_kernel): the f32
 // accumulators (C^T fragments: lane -> pixel row lane & 15, channels 4 (lane >> 4) + r) go through
@@ -214,25 +138,13 @@ template <int WM, int WN, int TM, int TN, int EPI>
 __device__ __forceinline__ void conv_store_tile(const f32x4 (&acc)[TM][TN], uint8_t *lds, uint16_t *__restrict__ y,
                                                 const Geo &g, const EpiArgs &ea, int m0, int n0, int tid,
                                                 float (&s1)[8], float (&s2)[8]) {
-    constexpr int WTM = 16 * TM, WTN = 16 * TN;
-    constexpr int BM = WTM * WM, BN = WTN * WN, NT = 64 * WM * WN;
-    constexpr int CROW = BN * 2 + 16;  // padded bytes per C row of the epilogue tile
-    constexpr bool STATS = (EPI & (kEpiFwdStats | kEpiBwdCoef | kEpiBwdBits | kEpiGate | kEpiGeluGrad)) != 0;
-    constexpr bool GATE = (EPI & kEpiGate) != 0;
-    constexpr bool GELUG = (EPI & kEpiGeluGrad) != 0;
-    constexpr bool BIAS = (EPI & (kEpiBiasRelu | kEpiBias)) != 0;
-    constexpr int NSUM = (GATE || GELUG) ? 1 : 2;  // the gates need sum(y) only (a bias gradient)
-    constexpr int VPR = BN / 8;  // 16-byte vectors per C row
-    constexpr int GROUPS = NT / VPR;
-    constexpr int ITER = BM * VPR / NT;  // 16-byte output vectors per thread per tile
-    static_assert(ITER * NT == BM * VPR, "whole store iterations");
-    constexpr bool LD_OLD = (EPI & kEpiAccum) != 0;
-    constexpr bool LD_BX = GATE || GELUG || (EPI & (kEpiBwdCoef | kEpiBwdBits)) != 0;
+    using T = EpiTile<WM, WN, TM, TN, EPI>;
+    constexpr int WTM = T::WTM, WTN = T::WTN, NT = T::NT, CROW = T::CROW, VPR = T::VPR, ITER = T::ITER;
+    constexpr bool STATS = T::STATS, GATE = T::GATE, GELUG = T::GELUG, BIAS = T::BIAS;
+    constexpr bool LD_OLD = T::LD_OLD, LD_BX = T::LD_BX;
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WN, wn = wave % WN;
-    const int cv = tid % (BN / 8);  // the epilogue's fixed 8-channel group of this thread
-    (void)STATS, (void)NSUM, (void)GROUPS, (void)LD_OLD, (void)LD_BX, (void)lane, (void)wm, (void)wn, (void)CROW,
-        (void)BIAS, (void)ITER;
+    const int cv = tid % VPR;  // the epilogue's fixed 8-channel group of this thread
 
     // ---- epilogue: bf16 tile through LDS, then 16-byte row stores
     // C^T map (16x16): pixel row = lane & 15, channel col = (lane >> 4) * 4 + r.
@@ -422,66 +334,42 @@ __device__ __forceinline__ void conv_store_tile(const f32x4 (&acc)[TM][TN], uint
 }
 
 // Per-channel statistics of a workgroup (s1 / s2 of every thread) -> f64 atomics into stats slot
-// `slot_sel % kStatSlots`, then the optional in-launch finalize.
-template <int WM, int WN, int TM, int TN, int EPI, int LDS_BYTES>
+// `slot_sel % kStatSlots`.
+template <int WM, int WN, int TM, int TN, int EPI>
 __device__ __forceinline__ void conv_stats_flush(uint8_t *lds, const Geo &g, const EpiArgs &ea, int n0, int tid,
-                                                 const float (&s1)[8], const float (&s2)[8], int slot_sel, int nwg,
-                                                 int orig) {
-    constexpr int WTM = 16 * TM, WTN = 16 * TN;
-    constexpr int BM = WTM * WM, BN = WTN * WN, NT = 64 * WM * WN;
-    constexpr int CROW = BN * 2 + 16;  // padded bytes per C row of the epilogue tile
-    constexpr bool STATS = (EPI & (kEpiFwdStats | kEpiBwdCoef | kEpiBwdBits | kEpiGate | kEpiGeluGrad)) != 0;
-    constexpr bool GATE = (EPI & kEpiGate) != 0;
-    constexpr bool GELUG = (EPI & kEpiGeluGrad) != 0;
-    constexpr bool BIAS = (EPI & (kEpiBiasRelu | kEpiBias)) != 0;
-    constexpr int NSUM = (GATE || GELUG) ? 1 : 2;  // the gates need sum(y) only (a bias gradient)
-    constexpr int VPR = BN / 8;  // 16-byte vectors per C row
-    constexpr int GROUPS = NT / VPR;
-    constexpr int ITER = BM * VPR / NT;  // 16-byte output vectors per thread per tile
-    static_assert(ITER * NT == BM * VPR, "whole store iterations");
-    constexpr bool LD_OLD = (EPI & kEpiAccum) != 0;
-    constexpr bool LD_BX = GATE || GELUG || (EPI & (kEpiBwdCoef | kEpiBwdBits)) != 0;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / WN, wn = wave % WN;
-    const int cv = tid % (BN / 8);  // the epilogue's fixed 8-channel group of this thread
-    (void)STATS, (void)NSUM, (void)GROUPS, (void)LD_OLD, (void)LD_BX, (void)lane, (void)wm, (void)wn, (void)CROW,
-        (void)BIAS, (void)ITER;
-    {
-        // reduce the NT / VPR threads of each channel group, then f64 atomics into a slot
-        float *red = reinterpret_cast<float *>(lds);
-        __syncthreads();
-        const int grp = tid / VPR;
+                                                 const float (&s1)[8], const float (&s2)[8], int slot_sel) {
+    using T = EpiTile<WM, WN, TM, TN, EPI>;
+    constexpr int BN = T::BN, NT = T::NT, NSUM = T::NSUM, VPR = T::VPR, GROUPS = T::GROUPS;
+    const int cv = tid % VPR;  // the epilogue's fixed 8-channel group of this thread
+    // reduce the NT / VPR threads of each channel group, then f64 atomics into a slot
+    float *red = reinterpret_cast<float *>(lds);
+    __syncthreads();
+    const int grp = tid / VPR;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            red[grp * BN + cv * 8 + k] = s1[k];
-            if constexpr (NSUM == 2) red[(GROUPS + grp) * BN + cv * 8 + k] = s2[k];
-        }
-        __syncthreads();
-        for (int col = tid; col < BN; col += NT) {
-            double t1 = 0, t2 = 0;
+    for (int k = 0; k < 8; ++k) {
+        red[grp * BN + cv * 8 + k] = s1[k];
+        if constexpr (NSUM == 2) red[(GROUPS + grp) * BN + cv * 8 + k] = s2[k];
+    }
+    __syncthreads();
+    for (int col = tid; col < BN; col += NT) {
+        double t1 = 0, t2 = 0;
 #pragma unroll 4
-            for (int p = 0; p < GROUPS; ++p) {
-                t1 += red[p * BN + col];
-                if constexpr (NSUM == 2) t2 += red[(GROUPS + p) * BN + col];
-            }
-            double *sl = ea.stats + (slot_sel % kStatSlots) * 2 * g.K;  // spread atomics over slots
-            if (n0 + col < g.K) {
-                atomicAdd(sl + n0 + col, t1);
-                if constexpr (NSUM == 2) atomicAdd(sl + g.K + n0 + col, t2);
-            }
+        for (int p = 0; p < GROUPS; ++p) {
+            t1 += red[p * BN + col];
+            if constexpr (NSUM == 2) t2 += red[(GROUPS + p) * BN + col];
         }
-        if constexpr (NSUM == 2) {
-            if (ea.fin != nullptr)
-                bn_finalize_last(ea.fin, ea.stats, g.K, nwg, orig, tid, NT, reinterpret_cast<double *>(lds),
-                                 LDS_BYTES / 8 - 2);
+        double *sl = ea.stats + (slot_sel % kStatSlots) * 2 * g.K;  // spread atomics over slots
+        if (n0 + col < g.K) {
+            atomicAdd(sl + n0 + col, t1);
+            if constexpr (NSUM == 2) atomicAdd(sl + g.K + n0 + col, t2);
         }
     }
 }
 
-// WM x WN waves (wave tile 64x64), STAGES-deep global_load_lds ring.
+// WM x WN waves (wave tile 64x64), STAGES-deep LDS-DMA ring.
 // KS = 3 or 1: square window; KS = 0xHW (>= 16): an H x W window (Inception's 1x7 / 7x1 / 1x3 /
 // 3x1 / 5x5, and the parity phases of a stride-2 3x3 data gradient, launch_conv_dgrad_s2).  The
-// zero padding is g.ph / g.pw (out-of-range taps read the zero page).  EPI flags (kernels.hpp ConvEpi):
+// zero padding is g.ph / g.pw (out-of-range taps read zeros).  EPI flags (kernels.hpp ConvEpi):
 //   kEpiAccum     y += conv (accumulate into the existing bf16 tensor, a residual gradient);
 //   kEpiFwdStats  per-channel sum / sum-of-squares of the bf16 outputs (the following BN's
 //                 batch statistics) -> f64 atomics into ea.stats[slot][2][K];
@@ -495,12 +383,9 @@ __device__ __forceinline__ void conv_stats_flush(uint8_t *lds, const Geo &g, con
 template <int KS, int WM, int WN, int STAGES, int EPI, int TM = 4, int TN = 4, bool PERSIST = false>
 __global__ __launch_bounds__(64 * WM * WN) void conv_kernel(const uint16_t *__restrict__ x,
                                                             const uint16_t *__restrict__ w,
-                                                            uint16_t *__restrict__ y,
-                                                            const uint16_t *__restrict__ zero, Geo g,
-                                                            EpiArgs ea) {
-    // wave tile (16*TM) x (16*TN): TM x TN accumulators of one 16x16x32 MFMA each
-    constexpr int WTM = 16 * TM, WTN = 16 * TN;
-    constexpr int BM = WTM * WM, BN = WTN * WN, NW = WM * WN, NT = 64 * NW;
+                                                            uint16_t *__restrict__ y, Geo g, EpiArgs ea) {
+    using T = EpiTile<WM, WN, TM, TN, EPI>;
+    constexpr int WTM = T::WTM, WTN = T::WTN, BM = T::BM, BN = T::BN, NW = WM * WN;
     constexpr int KH = KS >= 16 ? (KS >> 4) : KS, KW = KS >= 16 ? (KS & 15) : KS;
     constexpr int TAPS = KH * KW;
     constexpr int A_BYTES = BM * kRowBytes, B_BYTES = BN * kRowBytes;
@@ -515,22 +400,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_kernel(const uint16_t *__re
     constexpr int LOADS = A_INST + B_INST;
     static_assert(A_INST >= 1 && B_INST >= 1 && A_PIECES * 8 == BM && B_INST * NW * 8 == BN, "tile split");
     static_assert(A_EVEN || STAGES == 2, "uneven A split needs the 2-stage ring");
-    constexpr int CROW = BN * 2 + 16;  // padded bytes per C row of the epilogue tile
-    constexpr bool STATS = (EPI & (kEpiFwdStats | kEpiBwdCoef | kEpiBwdBits | kEpiGate | kEpiGeluGrad)) != 0;
-    constexpr bool GATE = (EPI & kEpiGate) != 0;
-    constexpr bool GELUG = (EPI & kEpiGeluGrad) != 0;
-    constexpr bool BIAS = (EPI & (kEpiBiasRelu | kEpiBias)) != 0;
-    constexpr int NSUM = (GATE || GELUG) ? 1 : 2;  // the gates need sum(y) only (a bias gradient)
-    constexpr int VPR = BN / 8;  // 16-byte vectors per C row
-    constexpr int GROUPS = NT / VPR;
-    constexpr int ITER = BM * VPR / NT;  // 16-byte output vectors per thread per tile
-    static_assert(ITER * NT == BM * VPR, "whole store iterations");
-    constexpr bool LD_OLD = (EPI & kEpiAccum) != 0;
-    constexpr bool LD_BX = GATE || GELUG || (EPI & (kEpiBwdCoef | kEpiBwdBits)) != 0;
-    // the statistics reduction reuses the C tile's LDS once the last tile is stored
-    constexpr int RED_BYTES = STATS ? NSUM * GROUPS * BN * 4 : 0;
-    constexpr int EPI_BYTES = BM * CROW > RED_BYTES ? BM * CROW : RED_BYTES;
-    constexpr int LDS_BYTES = STAGES * STAGE > EPI_BYTES ? STAGES * STAGE : EPI_BYTES;
+    constexpr int LDS_BYTES = STAGES * STAGE > T::EPI_BYTES ? STAGES * STAGE : T::EPI_BYTES;
     static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
     __shared__ __attribute__((aligned(1024))) uint8_t lds[LDS_BYTES];
 
@@ -542,7 +412,6 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_kernel(const uint16_t *__re
     const int mt_first = wg / g.ntiles, nt = wg - mt_first * g.ntiles;
     const int n0 = nt * BN;
     const int mstride = PERSIST ? nwg / g.ntiles : g.mtiles;  // nwg % ntiles == 0 when persistent
-    const int cv = tid % (BN / 8);  // the epilogue's fixed 8-channel group of this thread
     float s1[8], s2[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) s1[k] = s2[k] = 0.f;
@@ -584,7 +453,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_kernel(const uint16_t *__re
         }
     }
     // Channel counts that are not multiples of the tile (Inception's 48, 80, 96, 160, ...): the
-    // K-step's 8-channel chunks past Cin and the B rows past Cout read the zero page.
+    // K-step's 8-channel chunks past Cin and the B rows past Cout read zeros.
     int b_off[B_INST];
     uint32_t b_ok = 0;
 #pragma unroll
@@ -595,16 +464,13 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_kernel(const uint16_t *__re
     }
     const int csteps = (g.C + kBK - 1) / kBK;
     const int ksteps = TAPS * csteps;
-#if KUNGFU_CONV_BUFLD
     // LDS-DMA through buffer resources: 32-bit byte offsets, out-of-range lanes (padding taps,
     // channel chunks past Cin, B rows past Cout) get offset kBufOOB >= num_records and read
-    // zeros -- no 64-bit per-lane addresses, no zero-page select (the launcher checks that x and
-    // w are below 2 GiB).
+    // zeros -- no 64-bit per-lane addresses (the launcher checks that x and w are below 2 GiB).
     const __amdgpu_buffer_rsrc_t xr =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(x), 0, static_cast<int>(kBufOOB), kBufFlags);
     const __amdgpu_buffer_rsrc_t wr =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(w), 0, static_cast<int>(kBufOOB), kBufFlags);
-#endif
     auto stage = [&](int ks, int buf) {
         const int tap = ks / csteps, cc = ks - tap * csteps;
         const int kh = tap / KW, kw = tap - kh * KW;
@@ -618,25 +484,15 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_kernel(const uint16_t *__re
             const int piece = A_EVEN ? wave * A_INST + j : j * NW + wave;
             if (!A_EVEN && piece >= A_PIECES) break;  // wave-uniform
             const bool ok = ((a_ok[j] >> tap) & 1u) && cin_ok;
-#if KUNGFU_CONV_BUFLD
             const uint32_t vo = ok ? static_cast<uint32_t>(a_off[j] + toff) * 2u : kBufOOB;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, lds_ptr(abase + piece * 1024), 16, vo, 0, 0, 0);
-#else
-            const uint16_t *src = ok ? x + static_cast<uint32_t>(a_off[j] + toff) : zero;
-            __builtin_amdgcn_global_load_lds(src, abase + piece * 1024, 16, 0, 0);
-#endif
         }
 #pragma unroll
         for (int j = 0; j < B_INST; ++j) {
             const bool ok = ((b_ok >> j) & 1u) && cin_ok;
-#if KUNGFU_CONV_BUFLD
             const uint32_t vo = ok ? static_cast<uint32_t>(b_off[j] + wtap * g.C + cc * kBK) * 2u : kBufOOB;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, lds_ptr(bbase + (wave * B_INST + j) * 1024), 16, vo, 0, 0,
                                                      0);
-#else
-            const uint16_t *src = ok ? w + static_cast<uint32_t>(b_off[j] + wtap * g.C + cc * kBK) : zero;
-            __builtin_amdgcn_global_load_lds(src, bbase + (wave * B_INST + j) * 1024, 16, 0, 0);
-#endif
         }
     };
 
@@ -727,7 +583,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_kernel(const uint16_t *__re
     __syncthreads();  // all ds_reads of the last tile done before the LDS is reused
     conv_store_tile<WM, WN, TM, TN, EPI>(acc, lds, y, g, ea, m0, n0, tid, s1, s2);
     }  // m-tile loop
-    if constexpr (STATS) conv_stats_flush<WM, WN, TM, TN, EPI, LDS_BYTES>(lds, g, ea, n0, tid, s1, s2, mt_last + wg, nwg, orig);
+    if constexpr (T::STATS) conv_stats_flush<WM, WN, TM, TN, EPI>(lds, g, ea, n0, tid, s1, s2, mt_last + wg);
 }
 
 // Row-image 3x3 / stride-1 / pad-1 convolution (forward, and the stride-1 data gradient on
@@ -754,19 +610,14 @@ template <int WM, int WN, int BST, int EPI, int TM, int TN, int IMG, int IMGB, b
 __global__ __launch_bounds__(64 * WM * WN) void conv_rows_kernel(const uint16_t *__restrict__ x,
                                                                  const uint16_t *__restrict__ w,
                                                                  uint16_t *__restrict__ y, Geo g, EpiArgs ea) {
-    constexpr int WTM = 16 * TM, WTN = 16 * TN;
-    constexpr int BM = WTM * WM, BN = WTN * WN, NW = WM * WN, NT = 64 * NW;
+    using T = EpiTile<WM, WN, TM, TN, EPI>;
+    constexpr int WTM = T::WTM, WTN = T::WTN, BM = T::BM, BN = T::BN, NW = WM * WN;
     constexpr int B_BYTES = BN * kRowBytes, IMG_BYTES = IMG * kRowBytes;
     constexpr int B_INST = BN / 8 / NW;  // LDS-DMA pieces per wave per B stage (8 rows each)
     constexpr int I_INST = IMG / 8 / NW;  // ... per image
     static_assert(B_INST >= 1 && B_INST * NW * 8 == BN && I_INST * NW * 8 == IMG, "staging split");
-    constexpr int CROW = BN * 2 + 16;
-    constexpr bool STATS = (EPI & (kEpiFwdStats | kEpiBwdCoef | kEpiBwdBits | kEpiGate | kEpiGeluGrad)) != 0;
-    constexpr int NSUM = (EPI & (kEpiGate | kEpiGeluGrad)) ? 1 : 2;
-    constexpr int RED_BYTES = STATS ? NSUM * (NT / (BN / 8)) * BN * 4 : 0;
-    constexpr int EPI_BYTES = BM * CROW > RED_BYTES ? BM * CROW : RED_BYTES;
     constexpr int MAIN_BYTES = IMGB * IMG_BYTES + BST * B_BYTES;
-    constexpr int LDS_BYTES = MAIN_BYTES > EPI_BYTES ? MAIN_BYTES : EPI_BYTES;
+    constexpr int LDS_BYTES = MAIN_BYTES > T::EPI_BYTES ? MAIN_BYTES : T::EPI_BYTES;
     static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
     __shared__ __attribute__((aligned(1024))) uint8_t lds[LDS_BYTES];
 
@@ -912,8 +763,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_rows_kernel(const uint16_t 
         __syncthreads();
         conv_store_tile<WM, WN, TM, TN, EPI>(acc, lds, y, g, ea, m0, n0, tid, s1, s2);
     }  // m-tile loop
-    if constexpr (STATS)
-        conv_stats_flush<WM, WN, TM, TN, EPI, LDS_BYTES>(lds, g, ea, n0, tid, s1, s2, mt_last + wg, nwg, orig);
+    if constexpr (T::STATS) conv_stats_flush<WM, WN, TM, TN, EPI>(lds, g, ea, n0, tid, s1, s2, mt_last + wg);
 }
 
 // Largest image (padded-index range) any BM-pixel tile of this stride-1 3x3 geometry reads.
@@ -957,14 +807,6 @@ void launch_rows_epi(const uint16_t *x, const uint16_t *w, uint16_t *y, Geo g, c
             return;
         }
     }
-    if (ea.fin) {
-        EpiArgs e2 = ea;
-        e2.fin = nullptr;
-        conv_rows_kernel<WM, WN, BST, EPI, TM, TN, IMG, IMGB, false><<<g.mtiles * g.ntiles, 64 * WM * WN, 0, s>>>(
-            x, w, y, g, e2);
-        bn_fin_desc_kernel<<<(g.K + 255) / 256, 256, 0, s>>>(ea.fin, ea.stats, g.K);
-        return;
-    }
     conv_rows_kernel<WM, WN, BST, EPI, TM, TN, IMG, IMGB, false><<<g.mtiles * g.ntiles, 64 * WM * WN, 0, s>>>(
         x, w, y, g, ea);
 }
@@ -996,29 +838,17 @@ void launch_epi(const uint16_t *x, const uint16_t *w, uint16_t *y, Geo g, const 
     if constexpr (STATS) {
         // persistent blocks (4 per CU, fewer when the tile's LDS allows less): one atomic
         // statistics flush per block instead of per tile
-        constexpr int env_cap = 0;
         constexpr int kRow = 128, STG = ST * (BM + BN) * kRow, CT = BM * (BN * 2 + 16);
         constexpr int LDS = STG > CT ? STG : CT;
         constexpr int OCC = (160 * 1024) / LDS < 4 ? (160 * 1024) / LDS : 4;
-        const int cap = env_cap > 0 ? env_cap : 256 * (OCC < 1 ? 1 : OCC);
+        const int cap = 256 * (OCC < 1 ? 1 : OCC);
         const int per_n = cap / g.ntiles;
-        if (cap > 0 && per_n >= 1 && g.mtiles > 2 * per_n) {
-            conv_kernel<KS, WM, WN, ST, EPI, TM, TN, true><<<per_n * g.ntiles, 64 * WM * WN, 0, s>>>(
-                x, w, y, reinterpret_cast<const uint16_t *>(zero_page()), g, ea);
+        if (per_n >= 1 && g.mtiles > 2 * per_n) {
+            conv_kernel<KS, WM, WN, ST, EPI, TM, TN, true><<<per_n * g.ntiles, 64 * WM * WN, 0, s>>>(x, w, y, g, ea);
             return;
         }
     }
-    if (ea.fin) {
-        // one tile per workgroup: finalize in a launch of its own
-        EpiArgs e2 = ea;
-        e2.fin = nullptr;
-        conv_kernel<KS, WM, WN, ST, EPI, TM, TN><<<g.mtiles * g.ntiles, 64 * WM * WN, 0, s>>>(
-            x, w, y, reinterpret_cast<const uint16_t *>(zero_page()), g, e2);
-        bn_fin_desc_kernel<<<(g.K + 255) / 256, 256, 0, s>>>(ea.fin, ea.stats, g.K);
-        return;
-    }
-    conv_kernel<KS, WM, WN, ST, EPI, TM, TN><<<g.mtiles * g.ntiles, 64 * WM * WN, 0, s>>>(
-        x, w, y, reinterpret_cast<const uint16_t *>(zero_page()), g, ea);
+    conv_kernel<KS, WM, WN, ST, EPI, TM, TN><<<g.mtiles * g.ntiles, 64 * WM * WN, 0, s>>>(x, w, y, g, ea);
 }
 
 // Every fused epilogue on one tile shape.

@@ -18,14 +18,10 @@ void launch_phase_t(const uint16_t *dy, const uint16_t *wt, uint16_t *dx, Geo g,
     g.ntiles = (g.K + BN - 1) / BN;  // a partial last N tile reads zero B rows, stores its valid columns
     const int grid = g.mtiles * g.ntiles;
     check_buf_extent(g);
-    const uint16_t *z = reinterpret_cast<const uint16_t *>(zero_page());
-    EpiArgs e2 = ea;
-    e2.fin = nullptr;  // one tile per workgroup: the finalize runs as a launch of its own
-    if (epi == 0) conv_kernel<KS, WM, WN, ST, 0, TM, TN><<<grid, 64 * WM * WN, 0, s>>>(dy, wt, dx, z, g, e2);
-    else if (epi == C) conv_kernel<KS, WM, WN, ST, C, TM, TN><<<grid, 64 * WM * WN, 0, s>>>(dy, wt, dx, z, g, e2);
-    else if (epi == B) conv_kernel<KS, WM, WN, ST, B, TM, TN><<<grid, 64 * WM * WN, 0, s>>>(dy, wt, dx, z, g, e2);
+    if (epi == 0) conv_kernel<KS, WM, WN, ST, 0, TM, TN><<<grid, 64 * WM * WN, 0, s>>>(dy, wt, dx, g, ea);
+    else if (epi == C) conv_kernel<KS, WM, WN, ST, C, TM, TN><<<grid, 64 * WM * WN, 0, s>>>(dy, wt, dx, g, ea);
+    else if (epi == B) conv_kernel<KS, WM, WN, ST, B, TM, TN><<<grid, 64 * WM * WN, 0, s>>>(dy, wt, dx, g, ea);
     else throw std::invalid_argument("conv_dgrad_s2: unsupported epilogue");
-    if (ea.fin) bn_fin_desc_kernel<<<(g.K + 255) / 256, 256, 0, s>>>(ea.fin, ea.stats, g.K);
 }
 
 // Tile for the short-K phase GEMMs (variant >= 0 to override; tools/bench_dgrad_s2.py): 128x128
@@ -82,13 +78,8 @@ void launch_conv_dgrad_s2(const uint16_t *dy, const uint16_t *wt, uint16_t *dx, 
     // dy row a (one tap); q even -> kh = 2 at row a + q/2 - 1 and kh = 0 at row a + q/2 (two taps, the
     // window starting q/2 - 1 rows past a, i.e. zero padding 1 - q/2).  Same for columns.  Flipped-weight
     // tap index = 2 - kh; every dx pixel is written by exactly one phase.
-    if (ea.fin && (DH < 2 || DW < 2)) throw std::invalid_argument("conv_dgrad_s2: in-launch finalize needs dx >= 2x2");
-    // the BN-backward sums accumulate over all four phase launches: only the last one finalizes
-    EpiArgs ea_early = ea;
-    ea_early.fin = nullptr;
     for (int pr = 0; pr < 2; ++pr)
         for (int pc = 0; pc < 2; ++pc) {
-            const EpiArgs &eap = (pr == 1 && pc == 1) ? ea : ea_early;
             const int qr = pr + pad, qc = pc + pad;
             const int nh = (qr & 1) ? 1 : 2, nw = (qc & 1) ? 1 : 2;
             const int PH = (DH - pr + 1) / 2, PW = (DW - pc + 1) / 2;
@@ -103,10 +94,10 @@ void launch_conv_dgrad_s2(const uint16_t *dy, const uint16_t *wt, uint16_t *dx, 
             g.OH = PH, g.OW = PW, g.M = N * PH * PW;
             g.ph = nh == 1 ? 0 : 1 - qr / 2;
             g.pw = nw == 1 ? 0 : 1 - qc / 2;
-            if (nh == 1 && nw == 1) launch_phase<1>(dy, wt, dx, g, eap, epi, s, tv);
-            else if (nh == 1) launch_phase<0x12>(dy, wt, dx, g, eap, epi, s, tv);
-            else if (nw == 1) launch_phase<0x21>(dy, wt, dx, g, eap, epi, s, tv);
-            else launch_phase<0x22>(dy, wt, dx, g, eap, epi, s, tv);
+            if (nh == 1 && nw == 1) launch_phase<1>(dy, wt, dx, g, ea, epi, s, tv);
+            else if (nh == 1) launch_phase<0x12>(dy, wt, dx, g, ea, epi, s, tv);
+            else if (nw == 1) launch_phase<0x21>(dy, wt, dx, g, ea, epi, s, tv);
+            else launch_phase<0x22>(dy, wt, dx, g, ea, epi, s, tv);
         }
 }
 

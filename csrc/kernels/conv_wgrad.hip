@@ -61,22 +61,7 @@ struct WGeo {
 // Cache policy of the split-K kernel's LDS-DMA operand loads: non-temporal (aux = 2).  Measured
 // on the ResNet-50 step (r3h, tools/gpu_r3_ntconv.sh): +1 % with nt on both operands; the same
 // hint on the forward / data-gradient conv kernel's activation loads cost 1.5-2 %.
-#ifndef KUNGFU_WGRAD_AUX
-#define KUNGFU_WGRAD_AUX 2
-#endif
-constexpr int kWgradAux = KUNGFU_WGRAD_AUX;
-
-// Buffer-resource staging of wgrad_kernel's operands (num_records = 2 GiB; offset kWBufOOB
-// reads zeros).
-#ifndef KUNGFU_WGRAD_BUFLD
-#define KUNGFU_WGRAD_BUFLD 0
-#endif
-constexpr uint32_t kWBufOOB = 0x80000000u;
-constexpr int kWBufFlags = 0x00020000;
-
-__device__ __forceinline__ __attribute__((address_space(3))) void *wlds_ptr(uint8_t *p) {
-    return (__attribute__((address_space(3))) void *)(p);
-}
+constexpr int kWgradAux = 2;
 
 __device__ __forceinline__ int fdiv(int p, uint64_t m) {
     return static_cast<int>((static_cast<uint64_t>(static_cast<uint32_t>(p)) * m) >> 40);
@@ -166,15 +151,6 @@ __global__ __launch_bounds__(64 * WM * WN) void wgrad_kernel(const uint16_t *__r
         b_col[j] = n0 + lc * 8;
     }
 
-#if KUNGFU_WGRAD_BUFLD
-    // LDS-DMA through buffer resources (as conv.hip KUNGFU_CONV_BUFLD): 32-bit byte offsets, an
-    // out-of-range lane (pixel past P, channel past Cout / Cin, padding tap) reads zeros past
-    // num_records; the launcher checks that dy and x are below 2 GiB
-    const __amdgpu_buffer_rsrc_t dyr =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(dy), 0, static_cast<int>(kWBufOOB), kWBufFlags);
-    const __amdgpu_buffer_rsrc_t xr =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(x), 0, static_cast<int>(kWBufOOB), kWBufFlags);
-#endif
     auto stage = [&](int ks, int buf) {
         const int p0 = p_begin + ks * KB;
         uint8_t *abase = lds + buf * STAGE;
@@ -182,14 +158,8 @@ __global__ __launch_bounds__(64 * WM * WN) void wgrad_kernel(const uint16_t *__r
 #pragma unroll
         for (int j = 0; j < A_INST; ++j) {
             const int p = p0 + a_row[j];
-#if KUNGFU_WGRAD_BUFLD
-            const uint32_t vo = p < g.P && a_col[j] < g.K ? static_cast<uint32_t>(p * g.K + a_col[j]) * 2u : kWBufOOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(dyr, wlds_ptr(abase + (wave * A_INST + j) * 1024), 16, vo, 0, 0,
-                                                     kWgradAux);
-#else
             const uint16_t *src = p < g.P && a_col[j] < g.K ? dy + static_cast<uint32_t>(p * g.K + a_col[j]) : zero;
             __builtin_amdgcn_global_load_lds(src, abase + (wave * A_INST + j) * 1024, 16, 0, kWgradAux);
-#endif
         }
 #pragma unroll
         for (int j = 0; j < B_INST; ++j) {
@@ -207,13 +177,8 @@ __global__ __launch_bounds__(64 * WM * WN) void wgrad_kernel(const uint16_t *__r
                     static_cast<unsigned>(iw) < static_cast<unsigned>(g.W))
                     eo = static_cast<uint32_t>(((n * g.H + ih) * g.W + iw) * g.C + b_col[j]);
             }
-#if KUNGFU_WGRAD_BUFLD
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, wlds_ptr(bbase + (wave * B_INST + j) * 1024), 16,
-                                                     eo == 0xFFFFFFFFu ? kWBufOOB : eo * 2u, 0, 0, kWgradAux);
-#else
             const uint16_t *src = eo == 0xFFFFFFFFu ? zero : x + eo;
             __builtin_amdgcn_global_load_lds(src, bbase + (wave * B_INST + j) * 1024, 16, 0, kWgradAux);
-#endif
         }
     };
 
@@ -1041,26 +1006,9 @@ void launch_t(const uint16_t *dy, const uint16_t *x, void *dw, float *part, cons
     // staggered staging issue: on for the 256x256 tiles only -- BERT-base's long-K linear weight
     // gradients +1.5 % step time, ResNet-50's 256x128 tiles -0.8 % with it (tools/gpu_r3_envab.sh)
     const int stagger = TN == 8 ? 1 : 0;
-    if (KUNGFU_WGRAD_BUFLD && (static_cast<int64_t>(g.P) * g.K * 2 >= kWBufOOB ||
-                               static_cast<int64_t>(g.N) * g.H * g.W * g.C * 2 >= kWBufOOB))
-        throw std::invalid_argument("conv_wgrad: dy or x of 2 GiB or more (buffer-resource staging)");
-    // 256x256 tiles with four 32-pixel stages instead of two 64-pixel ones: measured no better (r4t1)
-    constexpr int kb32 = 0;
-    if constexpr (TN == 8) {
-        if (kb32) {
-            wgrad_kernel<KS, S, WM, WN, 4, TN, 32><<<g.tiles * g.splits, 64 * WM * WN, 0, s>>>(
-                dy, x, part, dw, reinterpret_cast<const uint16_t *>(zero_page()), g, out_f32, accumulate, atomic_out,
-                stagger);
-        } else {
-            wgrad_kernel<KS, S, WM, WN, STAGES, TN><<<g.tiles * g.splits, 64 * WM * WN, 0, s>>>(
-                dy, x, part, dw, reinterpret_cast<const uint16_t *>(zero_page()), g, out_f32, accumulate,
-                atomic_out, stagger);
-        }
-    } else {
-        wgrad_kernel<KS, S, WM, WN, STAGES, TN><<<g.tiles * g.splits, 64 * WM * WN, 0, s>>>(
-            dy, x, part, dw, reinterpret_cast<const uint16_t *>(zero_page()), g, out_f32, accumulate, atomic_out,
-            stagger);
-    }
+    // (256x256 tiles with four 32-pixel stages, KB = 32, instead of two 64-pixel ones: measured no better, r4t1)
+    wgrad_kernel<KS, S, WM, WN, STAGES, TN><<<g.tiles * g.splits, 64 * WM * WN, 0, s>>>(
+        dy, x, part, dw, reinterpret_cast<const uint16_t *>(zero_page()), g, out_f32, accumulate, atomic_out, stagger);
     if (g.splits > 1 && !atomic_out) {
         const int64_t total = static_cast<int64_t>(g.tiles) * (64 * WM) * (16 * TN * WN) / 4;
         int sgl = 0;  // split groups: enough blocks for the chip, at most 64 groups, <= splits

@@ -210,30 +210,7 @@ enum ConvEpi : int {
     // profiles/r5_prebn.md; the FC1 bias + GELU forward epilogue, 512, too -- slower end to end than
     // hipBLASLt + the GELU pass, profiles/r5t34_bert_g*.log)
 };
-// In-launch BN finalize of a statistics epilogue (kEpiFwdStats / kEpiBwdCoef / kEpiBwdBits): every
-// workgroup waits for its slot atomics, arrives on a two-level counter (per blockIdx % 8 shard,
-// then across shards), and the LAST arriver folds the kStatSlots slots (sc1 loads: the f64 adds
-// were performed at the memory side), writes what bn_sums_finalize / bn_bwd_finalize_sums would,
-// re-zeroes the slots and the counter -- the separate finalize launch (and its kernel boundary)
-// is gone.  The BN apply that follows is told the coefficients are already there.  Passed as a
-// pointer to a device copy (bn_fin_desc packs one on the host).
-struct BNFin {
-    int mode = 0;                // 0 off, 1 forward batch statistics, 2 backward sums
-    unsigned *arrive = nullptr;  // 9 zeroed words, left zeroed
-    int64_t rows = 0;            // elements per channel
-    int training = 1;            // backward: training-mode BN
-    const float *gamma = nullptr, *beta = nullptr;
-    float *mean = nullptr, *invstd = nullptr;  // forward: written; backward: read
-    float *run_mean = nullptr, *run_var = nullptr;
-    int64_t *num_batches = nullptr;
-    float momentum = 0.f, eps = 0.f;
-    float *coef = nullptr;                      // forward [scale; shift] (2C), backward (3C)
-    float *dgamma = nullptr, *dbeta = nullptr;  // backward
-};
 struct EpiArgs {
-    // device-resident descriptor (a kernel-argument copy of BNFin costs every statistics kernel
-    // ~25 spilled SGPRs: the compiler loads all kernel arguments up front)
-    const BNFin *fin = nullptr;
     const uint8_t *amask = nullptr;  // kEpiAccMask: ReLU mask of `old`, one byte per 8 channels
     const uint16_t *bias = nullptr;  // kEpiBiasRelu / kEpiBias: bf16 [K]
     double *stats = nullptr;         // kStatSlots x [2][K] f64 (zeroed; consumed + re-zeroed by the BN)
@@ -403,8 +380,8 @@ void launch_bn_forward(const uint16_t *x, const uint16_t *res, const float *gamm
                        float momentum, float eps, float *partial, float *mean, float *invstd, float *coef,
                        int64_t *num_batches, hipStream_t s, double *sums = nullptr, const float *res_coef = nullptr,
                        bool apply = true, int64_t y_ld = 0, bool prefinalized = false);
-// (prefinalized: mean / invstd / coef were already written from `sums` by the producing conv's
-// in-launch finalize (BNFin) -- no finalize launch here.
+// (prefinalized: mean / invstd / coef were already written from `sums` by the batched
+// bn_finalize_multi launch -- no finalize launch here.
 // (y_ld > 0: y is a channel slice of a wider NHWC tensor with that row stride (elements); BN+ReLU only.
 // (sums: f64 [2C] batch sums from a conv epilogue -> no statistics pass; re-zeroed.
 //  res_coef: the residual is res*res_coef[c] + res_coef[C+c] (another BN's input and
@@ -416,8 +393,7 @@ void launch_bn_backward(const uint16_t *dy, const uint16_t *x, const float *fcoe
                         const float *mean, const float *invstd, const float *gamma, BNShape sh, bool relu,
                         bool training, float *partial, float *dgamma, float *dbeta, float *coef, uint16_t *dx,
                         uint16_t *dres, hipStream_t s, double *sums = nullptr, const uint16_t *dres_x = nullptr,
-                        double *dres_sums = nullptr,
-                        int64_t dy_ld = 0, bool prefinalized = false, int phase = 0);
+                        double *dres_sums = nullptr, int64_t dy_ld = 0, int phase = 0);
 // (dres_x / dres_sums: dres also feeds a second, ReLU-free BN with input dres_x -- its backward
 //  sums go to dres_sums, zeroed f64 [slots][2][C])
 // (sums: f64 kStatSlots x [sum dz; sum dz*x] from a conv epilogue -> no reduce pass; re-zeroed.)

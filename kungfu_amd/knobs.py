@@ -11,8 +11,7 @@ Three kinds:
   alternative that measured slower, see profiles/README.md).  They are honoured ONLY when
   ``KUNGFU_DEV_KNOBS=1`` is also set -- in Python (:func:`get`) and in the kernels
   (``kfk::dev_knob``, csrc/kernels/common.hpp) -- so a stale shell variable cannot silently
-  slow a production run down.  Numerics-changing experiments are not knobs at all (e.g. the
-  BN-finalize skip is compiled in only with ``-DKUNGFU_DEV_EXPERIMENTS``).
+  slow a production run down.  Numerics-changing experiments are not knobs at all.
 
 :func:`check_environ` (called once at ``import kungfu_amd``) warns about every set ``KUNGFU_*``
 variable that is not registered (a misspelt knob would otherwise be ignored silently, with a
@@ -128,7 +127,7 @@ RETIRED: Dict[str, str] = {
     "KUNGFU_LINEAR_WGRAD_ATOMICS": "atomic split-K linear wgrad measured 3 % slower (r4t29)",
     "KUNGFU_GELU_FWD": "the one-exponential GELU forward measured 0.6 % slower (r4t20)",
     "KUNGFU_WGRAD_STREAM": "weight gradients on a side stream measured 1.2 % slower (r3)",
-    "KUNGFU_BN_INLAUNCH_FIN": "BN finalize inside the conv launch measured 0.55 ms/step slower (r3)",
+    "KUNGFU_BN_INLAUNCH_FIN": "the path is removed: BN finalize inside the conv launch measured 0.55 (r3) and 1.2 (r6) ms/step slower",
     "KUNGFU_CONV_PRIO": "s_setprio in the conv tiles measured neutral (r3)",
     "KUNGFU_STEM_FUSED_BWD": "the one-pass fused stem backward measured slower (r3)",
     "KUNGFU_COMM_STREAM_PRIORITY": "a high-priority comm stream measured 2x slower (r1)",
@@ -154,8 +153,7 @@ RETIRED: Dict[str, str] = {
 }
 
 # compile-time switches (-D...), not environment variables; listed so the source lint knows them
-MACROS = ("KUNGFU_CONV_BUFLD", "KUNGFU_WGRAD_BUFLD", "KUNGFU_WGRAD_AUX", "KUNGFU_DISABLE_TRACE",
-          "KUNGFU_ENABLE_TRACE", "KUNGFU_DEV_EXPERIMENTS", "KUNGFU_AMD_CAPI_H", "KUNGFU_ENABLE_HIP")
+MACROS = ("KUNGFU_DISABLE_TRACE", "KUNGFU_ENABLE_TRACE", "KUNGFU_AMD_CAPI_H", "KUNGFU_ENABLE_HIP")
 
 # prefixes with a free suffix (per-scope overrides)
 PREFIXES = ("KUNGFU_RCCL_MIN_CTAS_", "KUNGFU_RCCL_MAX_CTAS_")

@@ -76,92 +76,15 @@ def _cl(t: torch.Tensor) -> torch.Tensor:
 
 
 def _sums(bn, dev) -> torch.Tensor:
-    """Per-BN f64 statistics workspace (kept zeroed by the finalize kernel)."""
+    """Per-BN f64 statistics workspace (kept zeroed by the finalize kernel).  The finalize is a
+    launch of its own: skipping those launches altogether bounds the possible saving at 1.0 ms/step
+    on ResNet-50, and folding them into the statistics-producing conv (last-arriving workgroup)
+    measured 0.55-1.2 ms/step slower (profiles/README.md)."""
     ws = getattr(bn, "_kf_sums", None)
     if ws is None or ws.device != dev:
         ws = torch.zeros(hip().conv_stat_slots * 2 * bn.num_features, dtype=torch.float64, device=dev)
         bn._kf_sums = ws
     return ws
-
-
-# _INLAUNCH_FIN (module attribute; the retired KUNGFU_BN_INLAUNCH_FIN): the statistics-producing conv finalizes its BN in its own launch
-# (last-arriving workgroup, csrc/kernels/conv.hip bn_finalize_last; bit-identical).  Off by default:
-# measured 0.55-1.25 ms/step SLOWER on ResNet-50 than the separate finalize launches (every
-# workgroup must wait for its memory-side f64 slot atomics before it may arrive, and the arrivals
-# and the last workgroup's fold sit on the launch's critical path), although dropping the finalize
-# launches altogether would save 1.0 ms (KUNGFU_BN_SKIP_FINALIZE timing experiment).
-_INLAUNCH_FIN = False  # BN finalize inside the statistics conv (r3: 0.55 ms/step slower); a switch for its test
-
-
-def _kw(**kw):
-    """The keyword arguments that are not None (older extension builds lack fin / pre)."""
-    return {k: v for k, v in kw.items() if v is not None}
-
-
-class _BNFinState:
-    """Per-BN in-launch finalize state: the arrival counters and a ring of ``RING`` generations of
-    (output buffers, device descriptor) -- the forward's mean / invstd / coefficients and the
-    backward's dgamma / dbeta / coefficients live in persistent buffers the descriptors point at
-    (packed once, rebuilt only when a pointer or the row count changes).  A generation is reused
-    ``RING`` forwards later, so up to that many forwards may be outstanding before their backward."""
-    RING = 4
-
-    def __init__(self):
-        self.key = None
-        self.gen = 0
-        self.fwd = self.bwd = None
-
-    def _build(self, bn, gamma, beta, rows, dev):
-        H = hip()
-        C = bn.num_features
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.arrive = torch.zeros(16, dtype=torch.int32, device=dev)
-        self.fwd, self.bwd = [], []
-        for _ in range(self.RING):
-            mean, invstd, coef = torch.empty(C, **f32), torch.empty(C, **f32), torch.empty(2 * C, **f32)
-            d = H.bn_fin_desc(1, [self.arrive, gamma, beta, mean, invstd, coef, bn.running_mean, bn.running_var,
-                                  bn.num_batches_tracked], rows, float(bn.momentum), float(bn.eps), True).to(dev)
-            self.fwd.append((d, [mean, invstd, coef]))
-            dg, db, c3 = torch.empty(C, **f32), torch.empty(C, **f32), torch.empty(3 * C, **f32)
-            d2 = H.bn_fin_desc(2, [self.arrive, gamma, mean, invstd, c3, dg, db], rows, 0.0, 0.0, True).to(dev)
-            self.bwd.append((d2, [dg, db, c3]))
-
-    def next_fwd(self, bn, gamma, beta, rows, dev):
-        key = (gamma.data_ptr(), beta.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-               bn.num_batches_tracked.data_ptr(), int(rows), float(bn.momentum), float(bn.eps))
-        if key != self.key:
-            self._build(bn, gamma, beta, rows, dev)
-            self.key = key
-        g = self.gen
-        self.gen = (g + 1) % self.RING
-        return g
-
-
-def _fin_state(bn) -> _BNFinState:
-    st = getattr(bn, "_kf_fin", None)
-    if st is None:
-        st = bn._kf_fin = _BNFinState()
-    return st
-
-
-def _fin_fwd(bn, gamma, beta, rows, dev):
-    """(conv kwargs, bn_forward pre, generation) for a forward statistics epilogue that finalizes
-    in its own launch; the generation selects the backward buffers (:func:`_fin_bwd`)."""
-    if not _INLAUNCH_FIN:
-        return {}, None, None
-    st = _fin_state(bn)
-    g = st.next_fwd(bn, gamma, beta, rows, dev)
-    d, pre = st.fwd[g]
-    return dict(fin=d), pre, g
-
-
-def _fin_bwd(bn, gen):
-    """(fin descriptor, bn_backward pre) for the BN-backward-sums epilogue of the forward generation
-    ``gen`` (None: finalize separately)."""
-    if gen is None or not _INLAUNCH_FIN:
-        return None, None
-    d, pre = _fin_state(bn).bwd[gen]
-    return d, pre
 
 
 def _wgrad(dy, x, w, stride, pad):
@@ -223,19 +146,17 @@ def _dgrad(dy, x, w, stride, pad, out: Optional[torch.Tensor] = None, flipped: O
         wt = wt if wt is not None else H.conv_flip_weight(w)
         _dgrad.fused = bn is not None
         if bn is not None:
-            ws, bx, fc, mk = bn[:4]
-            fin = bn[4] if len(bn) > 4 else None
-            return H.conv(dy, wt, 1, ws, out, -1, bx, fc, mk, acc_mask=out_mask, acc_even=acc_even, **_kw(fin=fin))
+            ws, bx, fc, mk = bn
+            return H.conv(dy, wt, 1, ws, out, -1, bx, fc, mk, acc_mask=out_mask, acc_even=acc_even)
         return H.conv(dy, wt, 1, None, out, acc_mask=out_mask, acc_even=acc_even)
     assert out_mask is None and not acc_even
     ks = w.shape[2]
     if stride == 2 and out is None and _even_s2(x, dy, ks):
         wt = wt if wt is not None else H.conv_flip_weight(w)
         if ks == 3 and bn is not None:
-            ws, bx, fc, mk = bn[:4]
-            fin = bn[4] if len(bn) > 4 else None
+            ws, bx, fc, mk = bn
             _dgrad.fused = True
-            return H.conv_dgrad_s2(dy, wt, 3, ws, bx, fc, mk, **_kw(fin=fin))
+            return H.conv_dgrad_s2(dy, wt, 3, ws, bx, fc, mk)
         _dgrad.fused = False
         dx = H.conv_dgrad_s2(dy, wt, ks)
         if ks == 1:  # odd pixels get no gradient from a 1x1 stride-2 conv
@@ -271,13 +192,12 @@ class _TailSlot:
     BN3 backward sums (sum dz, sum dz*y3 under the 1-bit ReLU mask).  ``dx_ptr`` lets this
     block's backward check that the gradient it receives is exactly that tensor (no other
     consumer added to it); otherwise the sums are discarded and recomputed."""
-    __slots__ = ("ws", "y3", "mask", "ready", "dx_ptr", "fin", "pre")
+    __slots__ = ("ws", "y3", "mask", "ready", "dx_ptr")
 
-    def __init__(self, ws, y3, mask, fin=None, pre=None):
+    def __init__(self, ws, y3, mask):
         self.ws, self.y3, self.mask = ws, y3, mask
         self.ready = False
         self.dx_ptr = 0
-        self.fin, self.pre = fin, pre  # in-launch finalize of this block's BN3 backward (see _fin_bwd)
 
 
 class _Spec:
@@ -303,21 +223,13 @@ class _BottleneckFn(torch.autograd.Function):
         s = spec.stride
         outs = []
 
-        pres = [None] * len(spec.bns)
-
         def bn(i, y, res, relu, res_coef=None, apply=True):
             m = spec.bns[i]
             return H.bn_forward(y, res, gam[i], bet[i], m.running_mean, m.running_var, m.momentum, m.eps, True, relu,
-                                m.num_batches_tracked, _sums(m, dev), res_coef=res_coef, apply=apply, **_kw(pre=pres[i]))
-
-        gens = [None] * len(spec.bns)
+                                m.num_batches_tracked, _sums(m, dev), res_coef=res_coef, apply=apply)
 
         def conv(i, inp, w_, st_):
-            # the conv's statistics epilogue also finalizes BN i in its own launch (_fin_fwd)
-            oh = (inp.shape[2] - 1) // st_ + 1
-            ow = (inp.shape[3] - 1) // st_ + 1
-            kw, pres[i], gens[i] = _fin_fwd(spec.bns[i], gam[i], bet[i], inp.shape[0] * oh * ow, dev)
-            return H.conv(inp, w_, st_, _sums(spec.bns[i], dev), **kw)
+            return H.conv(inp, w_, st_, _sums(spec.bns[i], dev))
 
         y1 = conv(0, x, ws_bf[0], 1)
         z1, m1, i1, c1, _ = bn(0, y1, None, True)
@@ -335,9 +247,7 @@ class _BottleneckFn(torch.autograd.Function):
             out, m3, i3, c3, mask3 = bn(2, y3, x, True)
         # cross-block BN3 backward fusion: the previous block's tail (if x is its output)
         ctx.prev = getattr(x, "_kf_tail", None)
-        fin3, pre3 = _fin_bwd(spec.bns[2], gens[2])
-        ctx.tail = _TailSlot(_sums(spec.bns[2], dev), y3, mask3, fin3, pre3)
-        ctx.gens = gens
+        ctx.tail = _TailSlot(_sums(spec.bns[2], dev), y3, mask3)
         ctx.spec = spec
         ctx.wdtypes = [w.dtype for w in ws[0::3]]
         ctx.save_for_backward(x, y1, z1, y2, z2, y3, yd, *ws_bf, *gam, m1, i1, c1, m2, i2, c2, m3, i3, c3, mask3,
@@ -372,9 +282,7 @@ class _BottleneckFn(torch.autograd.Function):
         use3 = tail.ready and dout.data_ptr() == tail.dx_ptr
         if tail.ready and not use3:
             tail.ws.zero_()  # sums of a gradient that is not the one we got: discard
-            tail.pre = None  # (its in-launch finalize re-zeroed the slots; the coefficients are stale)
-        pre3 = tail.pre if use3 else None
-        tail.ready, tail.y3, tail.mask, tail.fin, tail.pre = False, None, None, None, None
+        tail.ready, tail.y3, tail.mask = False, None, None
         # identity block whose output gradient is our own buffer (the next block's conv1 data
         # gradient): the residual gradient dout * relu' is never written -- conv1's data
         # gradient below accumulates into dout in place, masking it on the fly
@@ -383,23 +291,21 @@ class _BottleneckFn(torch.autograd.Function):
         # sums are accumulated by this same pass (that BN then skips its reduce)
         dy3, didt, dg3, db3 = H.bn_backward(dout, y3, m3, i3, g[2], c3, mask3, True, True, not in_place,
                                             ws[2] if use3 else None, dres_x=yd if spec.ds else None,
-                                            dres_sums=ws[3] if spec.ds else None, **_kw(pre=pre3))
+                                            dres_sums=ws[3] if spec.ds else None)
         dbn[2] = (dg3, db3)
         if _CAPTURE is not None:
             _capture(spec.bns[2], "mask", dout, y3, m3, i3, mask3, dg3, db3)
-        fin2, pre2 = _fin_bwd(spec.bns[1], ctx.gens[1])
-        dz2 = _dgrad(dy3, z2, w[2], 1, 0, flipped=fl[2], bn=(ws[1], y2, c2, None, fin2))
+        dz2 = _dgrad(dy3, z2, w[2], 1, 0, flipped=fl[2], bn=(ws[1], y2, c2, None))
         dw[2] = wgrad(dy3, z2, w[2], 1, 0)
-        dy2, _, dg2, db2 = H.bn_backward(dz2, y2, m2, i2, g[1], c2, None, True, True, False, ws[1], **_kw(pre=pre2))
+        dy2, _, dg2, db2 = H.bn_backward(dz2, y2, m2, i2, g[1], c2, None, True, True, False, ws[1])
         dbn[1] = (dg2, db2)
         if _CAPTURE is not None:
             _capture(spec.bns[1], "relu", dz2, y2, m2, i2, c2, dg2, db2)
-        fin1, pre1 = _fin_bwd(spec.bns[0], ctx.gens[0])
-        dz1 = _dgrad(dy2, z1, w[1], s, 1, flipped=fl[1], bn=(ws[0], y1, c1, None, fin1))
+        dz1 = _dgrad(dy2, z1, w[1], s, 1, flipped=fl[1], bn=(ws[0], y1, c1, None))
         fused1 = _dgrad.fused
         dw[1] = wgrad(dy2, z1, w[1], s, 1)
         dy1, _, dg1, db1 = H.bn_backward(dz1, y1, m1, i1, g[0], c1, None, True, True, False,
-                                         ws[0] if fused1 else None, **_kw(pre=pre1 if fused1 else None))
+                                         ws[0] if fused1 else None)
         dbn[0] = (dg1, db1)
         if _CAPTURE is not None:
             _capture(spec.bns[0], "relu", dz1, y1, m1, i1, c1, dg1, db1)
@@ -425,7 +331,7 @@ class _BottleneckFn(torch.autograd.Function):
         if prev is not None and prev.y3 is not None and prev.y3.shape == dx.shape:
             # conv1's data gradient completes the gradient of the previous block's output:
             # its epilogue also accumulates that block's BN3 backward sums
-            dx = _dgrad(dy1, x, w[0], 1, 0, out=dx, flipped=fl[0], bn=(prev.ws, prev.y3, None, prev.mask, prev.fin),
+            dx = _dgrad(dy1, x, w[0], 1, 0, out=dx, flipped=fl[0], bn=(prev.ws, prev.y3, None, prev.mask),
                         out_mask=om, acc_even=acc_even)
             prev.ready, prev.dx_ptr = True, dx.data_ptr()
         else:

@@ -25,9 +25,10 @@ def _cl(t):
 
 
 # (variant, N, H, Cin, Cout): 20 / 23 need Cin = 64 (one image buffer); odd N and small maps put
-# image boundaries and the end of M inside tiles
+# image boundaries and the end of M inside tiles; (24, 85, ...): 1,042 m-tiles of 256 pixels, more than
+# the 2 x 512 resident blocks, so the persistent statistics blocks walk 2-3 tiles each
 CASES = [(20, 3, 56, 64, 64), (20, 5, 9, 64, 64), (23, 3, 56, 64, 64), (23, 2, 13, 64, 128), (24, 3, 56, 64, 64),
-         (25, 3, 56, 64, 64), (25, 2, 13, 64, 128),
+         (24, 85, 56, 64, 64), (25, 3, 56, 64, 64), (25, 2, 13, 64, 128),
          (21, 3, 28, 128, 128), (21, 5, 14, 256, 256), (21, 3, 7, 512, 512), (21, 2, 11, 192, 128),
          (22, 3, 28, 128, 128), (22, 4, 7, 512, 512), (22, 3, 10, 64, 256)]
 
@@ -53,7 +54,8 @@ def test_conv_rows_forward_stats(variant, N, H, C, K):
 
 @needs_gpu
 @pytest.mark.parametrize("variant,N,H,C,K", [(20, 3, 56, 64, 64), (23, 2, 13, 128, 64), (21, 3, 28, 128, 128),
-                                             (21, 5, 14, 256, 256), (22, 4, 7, 512, 512), (22, 3, 10, 256, 64)])
+                                             (21, 5, 14, 256, 256), (22, 4, 7, 512, 512), (22, 3, 10, 256, 64),
+                                             (24, 85, 56, 64, 64)])
 def test_conv_rows_data_gradient_bn_sums(variant, N, H, C, K):
     """The stride-1 data gradient (the conv on flipped weights) with the BN-backward-sums epilogue
     of the BN(+ReLU) whose input is bn_x: dz = grad * relu'(bn_x * scale + shift)."""

@@ -1,6 +1,6 @@
 """Run bench.py with module attributes overridden (same-box A/B of settled-off paths).
 
-    python tools/bench_switch.py kungfu_amd.ops.fused_block:_INLAUNCH_FIN=True -- --steps 20 --warmup 5
+    python tools/bench_switch.py kungfu_amd.ops.fused_bn:_BATCH_FIN=False -- --steps 20 --warmup 5
 
 Each ``module:attr=value`` is imported and set before bench.main() runs (value parsed as a Python
 literal).  Only for measurements: the switches named here are dev paths, not user knobs.
