@@ -76,3 +76,91 @@ def check_bn_param_grads(ref: Tuple[torch.Tensor, torch.Tensor], got: Tuple[torc
         if not e <= tol:
             return "%s relative error %.3g > %.3g" % (name, e, tol)
     return None
+
+
+# ---- bit-exact checks of the MFMA kernels on integer data ---------------------------------------
+#
+# With small-integer operands every product and every f32 partial sum of a convolution / GEMM is an
+# exact integer, so the result does not depend on the summation order, the tile shape, the split
+# count or atomics: a kernel's output must equal a float64 reference bit for bit, and one wrong
+# element fails the comparison (a whole-tensor relative L2 of 1e-2 accepts a pixel that lost a tap,
+# and either 1e-2 criterion accepts truncation in place of round-to-nearest-even:
+# tests/test_numerics_helper.py).
+
+_F32_EXACT = float(1 << 24)  # integers up to 2^24 are exact in f32 (every partial sum)
+_BF16_EXACT = 256.0          # integers up to 2^8 are exact in bf16 (8 significand bits)
+
+
+def integer_data(shape, kind: str = "sparse", seed: int = 0, device="cpu", hi: int = 4) -> torch.Tensor:
+    """A float32 tensor of small integers (cast it to bf16: every value is exact there), drawn on the
+    CPU from ``seed`` -- the same values whatever ``device`` it is moved to.
+
+    ``"sparse"``: {-1, 0, 1} with P(non-zero) = 1/4 (the default operand: sums over thousands of
+    terms stay within 256); ``"dense"``: {-2, -1, 1, 2}, never zero -- the activation operand next
+    to a sparse weight, so a read of the wrong address cannot hide behind a zero; ``"ties"``:
+    non-negative integers in [0, hi) -- with {0, 1} weights (``hi=2``) the sums pass 256, where odd
+    integers lie exactly halfway between two bf16 values and exercise the rounding mode."""
+    g = torch.Generator().manual_seed(seed)
+    if kind == "sparse":
+        r = torch.randint(0, 8, shape, generator=g)
+        t = (r == 0).float() - (r == 1).float()
+    elif kind == "dense":
+        r = torch.randint(0, 4, shape, generator=g)
+        t = torch.tensor([-2.0, -1.0, 1.0, 2.0])[r]
+    elif kind == "ties":
+        t = torch.randint(0, hi, shape, generator=g).float()
+    else:
+        raise ValueError(kind)
+    return t.to(device)
+
+
+def tie_fraction(ref_f64: torch.Tensor) -> float:
+    """Share of the elements that lie exactly halfway between two adjacent bf16 values (where
+    round-to-nearest-even, round-half-away and truncation all differ)."""
+    r = ref_f64.double()
+    f = r.float()
+    assert torch.equal(f.double(), r), "tie_fraction: the reference is not exact in f32"
+    low = f.contiguous().view(torch.int32) & 0xFFFF
+    return (low == 0x8000).double().mean().item()
+
+
+def _canon_bits(t: torch.Tensor) -> torch.Tensor:
+    """Bit patterns with -0 folded onto +0 (the sign of an exact zero sum depends on the order of
+    the additions, in the reference as in the kernel)."""
+    t = t.contiguous()
+    t = torch.where(t == 0, torch.zeros_like(t), t)
+    return t.view({2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
+
+
+def check_exact_reference(ref_f64: torch.Tensor, dtype: torch.dtype, ties: bool = False, what: str = "") -> None:
+    """The preconditions under which a kernel's ``dtype`` output must equal ``ref_f64`` bit for bit:
+    integer-valued, below 2^24 in magnitude (exact in every f32 partial sum) and, for a bf16 output
+    outside the ties kind, within 256 (exact in bf16).  Raises AssertionError, never skips."""
+    assert ref_f64.dtype == torch.float64, "%s: the reference must be float64" % what
+    assert torch.isfinite(ref_f64).all(), "%s: non-finite reference" % what
+    assert torch.equal(ref_f64, ref_f64.round()), "%s: the reference is not integer-valued" % what
+    mx = ref_f64.abs().max().item() if ref_f64.numel() else 0.0
+    assert mx < _F32_EXACT, "%s: reference magnitude %g is not exact in f32 partial sums" % (what, mx)
+    if dtype == torch.bfloat16 and not ties:
+        assert mx <= _BF16_EXACT, "%s: reference magnitude %g is not exact in bf16" % (what, mx)
+
+
+def assert_bits_equal(got: torch.Tensor, ref_f64: torch.Tensor, what: str = "", ties: bool = False) -> None:
+    """``got`` (bf16 / f32 / f64, any layout) equals ``ref_f64`` rounded to its dtype by torch's own
+    f64 -> f32 -> dtype conversion (round-to-nearest-even), bit for bit.  The preconditions are
+    enforced on the reference alone (:func:`check_exact_reference`).  A mismatch reports the count,
+    the first indices and got / expected at each, so a failure names the pixel and the channel."""
+    check_exact_reference(ref_f64, got.dtype, ties, what)
+    assert tuple(got.shape) == tuple(ref_f64.shape), "%s: shape %s vs reference %s" % (
+        what, tuple(got.shape), tuple(ref_f64.shape))
+    exp = ref_f64.to(got.device)
+    exp = exp if got.dtype == torch.float64 else exp.float().to(got.dtype)
+    g = got.detach().contiguous()  # logical (NCHW) element order: indices read as [n, c, h, w]
+    bad = _canon_bits(g) != _canon_bits(exp)
+    n = int(bad.sum().item())
+    if n == 0:
+        return
+    idx = bad.nonzero()[:8].cpu()
+    lines = ["%s  got %r  expected %r" % (tuple(i.tolist()), g[tuple(i)].item(), exp[tuple(i)].item()) for i in idx]
+    raise AssertionError("%s: %d of %d elements differ from the exact reference; first:\n  %s" % (
+        what, n, g.numel(), "\n  ".join(lines)))
