@@ -1502,15 +1502,17 @@ at::Tensor stem_wgrad(at::Tensor dy, at::Tensor x4, int64_t splits) {
     return dw;
 }
 
-// Small image stem (stem3.hip, Inception's Conv2d_1a): w [32, 3, KH, KW] channels_last bf16 -> packed [32, 64]
+// Small image stems (stem3.hip: Inception's Conv2d_1a, VGG-16's first layer): w [32|64, 3, KH, KW] channels_last
+// bf16 -> packed [Cout, 64]
 at::Tensor stem3_pack_weight(at::Tensor w) {
-    TORCH_CHECK(w.is_cuda() && w.scalar_type() == at::kBFloat16 && w.dim() == 4 && w.size(0) == 32 && w.size(1) == 3 &&
-                    w.size(2) <= 4 && w.size(3) <= 4 && w.is_contiguous(at::MemoryFormat::ChannelsLast),
-                "stem3_pack_weight: w must be [32, 3, KH<=4, KW<=4] channels_last bf16");
+    TORCH_CHECK(w.is_cuda() && w.scalar_type() == at::kBFloat16 && w.dim() == 4 && (w.size(0) == 32 || w.size(0) == 64) &&
+                    w.size(1) == 3 && w.size(2) <= 4 && w.size(3) <= 4 && w.is_contiguous(at::MemoryFormat::ChannelsLast),
+                "stem3_pack_weight: w must be [32|64, 3, KH<=4, KW<=4] channels_last bf16");
     c10::DeviceGuard gd(w.device());
-    auto wp = at::empty({32, 64}, w.options().memory_format(at::MemoryFormat::Contiguous));
+    auto wp = at::empty({w.size(0), 64}, w.options().memory_format(at::MemoryFormat::Contiguous));
     kfk::launch_stem3_pack_weight(reinterpret_cast<const uint16_t *>(w.data_ptr()),
-                                  reinterpret_cast<uint16_t *>(wp.data_ptr()), w.size(2), w.size(3), stream_of(w, 0));
+                                  reinterpret_cast<uint16_t *>(wp.data_ptr()), w.size(0), w.size(2), w.size(3),
+                                  stream_of(w, 0));
     return wp;
 }
 
@@ -1520,45 +1522,77 @@ static void check_img3(const at::Tensor &x, const char *name) {
                 name, ": x must be the [N, 3, H, W] channels_last f32 / bf16 image");
 }
 
+// out (optional): the [N, Cout, OH, OW] channels_last bf16 tensor to write (else a new one)
 at::Tensor stem3_forward(at::Tensor x, at::Tensor wp, int64_t kh, int64_t kw, int64_t stride, int64_t ph, int64_t pw,
-                         c10::optional<at::Tensor> stats) {
+                         c10::optional<at::Tensor> stats, c10::optional<at::Tensor> bias, bool relu,
+                         c10::optional<at::Tensor> out) {
     check_img3(x, "stem3_forward");
-    TORCH_CHECK(wp.scalar_type() == at::kBFloat16 && wp.numel() == 32 * 64 && wp.is_contiguous() &&
-                    wp.device() == x.device(),
-                "stem3_forward: wp must be the packed [32, 64] weights");
+    TORCH_CHECK(wp.scalar_type() == at::kBFloat16 && wp.dim() == 2 && (wp.size(0) == 32 || wp.size(0) == 64) &&
+                    wp.size(1) == 64 && wp.is_contiguous() && wp.device() == x.device(),
+                "stem3_forward: wp must be the packed [32|64, 64] weights");
+    const int Cout = wp.size(0);
     const int N = x.size(0), H = x.size(2), W = x.size(3);
     double *sp = nullptr;
     if (stats && stats->defined()) {
-        TORCH_CHECK(stats->is_cuda() && stats->scalar_type() == at::kDouble && stats->numel() == 2 * 32 * kfk::kStatSlots &&
-                        stats->is_contiguous() && stats->device() == x.device(),
-                    "stem3_forward: stats must be a contiguous f64 [slots*2*32] tensor");
+        TORCH_CHECK(stats->is_cuda() && stats->scalar_type() == at::kDouble &&
+                        stats->numel() == 2 * Cout * kfk::kStatSlots && stats->is_contiguous() &&
+                        stats->device() == x.device(),
+                    "stem3_forward: stats must be a contiguous f64 [slots*2*Cout] tensor");
         sp = stats->data_ptr<double>();
+    }
+    const float *bp = nullptr;
+    if (bias && bias->defined()) {
+        TORCH_CHECK(bias->is_cuda() && bias->scalar_type() == at::kFloat && bias->dim() == 1 && bias->size(0) == Cout &&
+                        bias->is_contiguous() && bias->device() == x.device(),
+                    "stem3_forward: bias must be a contiguous f32 [Cout] tensor on x's device");
+        bp = bias->data_ptr<float>();
     }
     c10::DeviceGuard gd(x.device());
     const int OH = kfk::stem3_out(H, kh, stride, ph), OW = kfk::stem3_out(W, kw, stride, pw);
     TORCH_CHECK(OH > 0 && OW > 0, "stem3_forward: empty output");
-    auto y = at::empty({N, 32, OH, OW}, x.options().dtype(at::kBFloat16).memory_format(at::MemoryFormat::ChannelsLast));
+    at::Tensor y;
+    if (out && out->defined()) {
+        y = *out;
+        TORCH_CHECK(y.scalar_type() == at::kBFloat16 && y.dim() == 4 && y.size(0) == N && y.size(1) == Cout &&
+                        y.size(2) == OH && y.size(3) == OW && y.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+                        y.device() == x.device(),
+                    "stem3_forward: out must be a [N, Cout, OH, OW] channels_last bf16 tensor on x's device");
+    } else {
+        y = at::empty({N, Cout, OH, OW}, x.options().dtype(at::kBFloat16).memory_format(at::MemoryFormat::ChannelsLast));
+    }
     kfk::launch_stem3_forward(x.data_ptr(), x.scalar_type() == at::kFloat, reinterpret_cast<const uint16_t *>(wp.data_ptr()),
-                              reinterpret_cast<uint16_t *>(y.data_ptr()), sp, N, H, W, kh, kw, stride, ph, pw,
-                              stream_of(x, 0));
+                              reinterpret_cast<uint16_t *>(y.data_ptr()), sp, bp, relu, Cout, N, H, W, kh, kw, stride, ph,
+                              pw, stream_of(x, 0));
     return y;
 }
 
+// out (optional): the [Cout, 3, KH, KW] channels_last tensor (f32 if out_f32, else bf16) to write
 at::Tensor stem3_wgrad(at::Tensor dy, at::Tensor x, int64_t kh, int64_t kw, int64_t stride, int64_t ph, int64_t pw,
-                       bool out_f32) {
+                       bool out_f32, c10::optional<at::Tensor> out) {
     check_img3(x, "stem3_wgrad");
     const int N = x.size(0), H = x.size(2), W = x.size(3);
     const int OH = kfk::stem3_out(H, kh, stride, ph), OW = kfk::stem3_out(W, kw, stride, pw);
-    TORCH_CHECK(dy.scalar_type() == at::kBFloat16 && dy.dim() == 4 && dy.size(0) == N && dy.size(1) == 32 &&
-                    dy.size(2) == OH && dy.size(3) == OW && dy.is_contiguous(at::MemoryFormat::ChannelsLast) &&
-                    dy.device() == x.device(),
-                "stem3_wgrad: dy must be the [N, 32, OH, OW] channels_last bf16 output gradient");
+    TORCH_CHECK(kh >= 1 && kh <= 4 && kw >= 1 && kw <= 4, "stem3_wgrad: window <= 4x4");
+    TORCH_CHECK(dy.scalar_type() == at::kBFloat16 && dy.dim() == 4 && dy.size(0) == N &&
+                    (dy.size(1) == 32 || dy.size(1) == 64) && dy.size(2) == OH && dy.size(3) == OW &&
+                    dy.is_contiguous(at::MemoryFormat::ChannelsLast) && dy.device() == x.device(),
+                "stem3_wgrad: dy must be the [N, 32|64, OH, OW] channels_last bf16 output gradient");
+    const int Cout = dy.size(1);
     c10::DeviceGuard gd(x.device());
-    auto part = at::empty({kfk::stem3_wgrad_workspace(N, H, W, kh, kw, stride, ph, pw)}, x.options().dtype(at::kFloat));
-    auto dw = at::empty({32, 3, kh, kw}, x.options().dtype(out_f32 ? at::kFloat : at::kBFloat16)
-                                            .memory_format(at::MemoryFormat::ChannelsLast));
+    auto part = at::empty({kfk::stem3_wgrad_workspace(Cout, N, H, W, kh, kw, stride, ph, pw)},
+                          x.options().dtype(at::kFloat));
+    const auto dt = out_f32 ? at::kFloat : at::kBFloat16;
+    at::Tensor dw;
+    if (out && out->defined()) {
+        dw = *out;
+        TORCH_CHECK(dw.scalar_type() == dt && dw.dim() == 4 && dw.size(0) == Cout && dw.size(1) == 3 && dw.size(2) == kh &&
+                        dw.size(3) == kw && dw.is_contiguous(at::MemoryFormat::ChannelsLast) && dw.device() == x.device(),
+                    "stem3_wgrad: out must be a [Cout, 3, KH, KW] channels_last tensor of the output dtype on x's device");
+    } else {
+        dw = at::empty({Cout, 3, kh, kw}, x.options().dtype(dt).memory_format(at::MemoryFormat::ChannelsLast));
+    }
     kfk::launch_stem3_wgrad(reinterpret_cast<const uint16_t *>(dy.data_ptr()), x.data_ptr(), x.scalar_type() == at::kFloat,
-                            dw.data_ptr(), out_f32, part.data_ptr<float>(), N, H, W, kh, kw, stride, ph, pw,
+                            dw.data_ptr(), out_f32, part.data_ptr<float>(), Cout, N, H, W, kh, kw, stride, ph, pw,
                             stream_of(x, 0));
     return dw;
 }
@@ -1985,13 +2019,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("out") = py::none(), py::arg("variant") = -1, py::arg("bn_x") = py::none(),
           py::arg("bn_fcoef") = py::none(), py::arg("bn_mask") = py::none(), py::arg("bias") = py::none(),
           py::arg("gate") = false, py::arg("acc_mask") = py::none(), py::arg("acc_even") = false);
-    m.def("stem3_pack_weight", &stem3_pack_weight, "pack [32, 3, KH, KW] stem weights for stem3_forward");
-    m.def("stem3_forward", &stem3_forward, "small image-stem conv (<= 4x4 window, 3 -> 32 channels) with the BN-sums "
-          "epilogue", py::arg("x"), py::arg("wp"), py::arg("kh"), py::arg("kw"), py::arg("stride"), py::arg("ph"),
-          py::arg("pw"), py::arg("stats") = py::none());
+    m.def("stem3_pack_weight", &stem3_pack_weight, "pack [32|64, 3, KH, KW] stem weights for stem3_forward");
+    m.def("stem3_forward", &stem3_forward, "small image-stem conv (<= 4x4 window, 3 -> 32 | 64 channels) with optional "
+          "f32 bias (+ ReLU) and BN-sums epilogues", py::arg("x"), py::arg("wp"), py::arg("kh"), py::arg("kw"),
+          py::arg("stride"), py::arg("ph"), py::arg("pw"), py::arg("stats") = py::none(), py::arg("bias") = py::none(),
+          py::arg("relu") = false, py::arg("out") = py::none());
     m.def("stem3_wgrad", &stem3_wgrad, "its weight gradient (MFMA over pixels, deterministic)", py::arg("dy"),
           py::arg("x"), py::arg("kh"), py::arg("kw"), py::arg("stride"), py::arg("ph"), py::arg("pw"),
-          py::arg("out_f32") = false);
+          py::arg("out_f32") = false, py::arg("out") = py::none());
     m.def("conv_rect", &conv_rect, "KH x KW NHWC bf16 convolution with zero padding (MFMA implicit GEMM; "
           "Inception-v3 windows) with an optional BN-statistics epilogue", py::arg("x"), py::arg("w"),
           py::arg("stride") = 1, py::arg("ph") = 0, py::arg("pw") = 0, py::arg("stats") = py::none(),

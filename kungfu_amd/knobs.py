@@ -94,7 +94,7 @@ KNOBS: Dict[str, Knob] = {
     "KUNGFU_WGRAD": _u("1", "weight gradients on the split-K MFMA kernel"),
     "KUNGFU_WGRAD_RECT": _u("1", "rectangular-window weight gradients on the MFMA kernels"),
     "KUNGFU_FUSED_BLOCK": _u("1", "ResNet bottleneck as one fused autograd node"),
-    "KUNGFU_STEM": _u("1", "ResNet stem conv on the MFMA stem kernel"),
+    "KUNGFU_STEM": _u("1", "image stem convs (ResNet 7x7, Inception Conv2d_1a, VGG first layer) on the MFMA stem kernels"),
     "KUNGFU_LINEAR_WGRAD": _u("1", "linear-layer weight gradients on the split-K MFMA kernel"),
     "KUNGFU_DEV_KNOBS": _u("0", "1: honour the dev (A/B) knobs below"),
     # -- launcher / worker env contract (csrc/launcher/job.cpp, csrc/runtime/peer.cpp) ---------

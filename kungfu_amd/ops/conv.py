@@ -385,6 +385,12 @@ class Conv2dReLU(nn.Conv2d):
 
         w = shadow(self.weight)
         b = shadow(self.bias) if self.bias is not None else None
+        if b is not None and x.dim() == 4 and x.shape[1] == 3:
+            from .stem import stem3_conv, stem3_eligible
+
+            if stem3_eligible(self, x):
+                # the 3-channel image layer (VGG-16's first) on stem3.hip: bias + ReLU in the conv epilogue
+                return stem3_conv(self, x, w, bias=b, relu=True)
         if self.padding_mode == "zeros" and x.dtype == torch.bfloat16:
             return conv2d(x, w, b, self.stride, self.padding, self.dilation, self.groups, relu=True)
         if b is not None and x.is_cuda and hip_available() and hip().bias_act_supported(self.out_channels):

@@ -8,8 +8,9 @@ the BN batch statistics in the conv epilogue, so ``bn_pool_forward(..., sums=sta
 its statistics pass.  The image is cast to bf16 and padded to 4 channels in one pass; the
 weight gradient is the split-K MFMA kernel; the image gets no gradient.
 
-Set ``KUNGFU_STEM=0`` to use MIOpen.  No reference counterpart (the reference trains
-``tf.keras.applications`` ResNet-50, ``benchmarks/system/benchmark_kungfu.py:96``).
+Set ``KUNGFU_STEM=0`` to use MIOpen (for this stem and the small image stems below).  No
+reference counterpart (the reference trains ``tf.keras.applications`` ResNet-50,
+``benchmarks/system/benchmark_kungfu.py:96``).
 """
 from __future__ import annotations
 
@@ -136,8 +137,10 @@ def stem_block(x: torch.Tensor, w: torch.Tensor, bn, sums: Optional[torch.Tensor
 
 
 # ---------------------------------------------------------------------------------------------
-# Small image stems (csrc/kernels/stem3.hip): a <= 4x4 window over the 3-channel image, 32 output
-# channels, any stride / zero padding -- Inception-v3's Conv2d_1a (3x3, stride 2, no padding).
+# Small image stems (csrc/kernels/stem3.hip): a <= 4x4 window over the 3-channel image, 32 or 64 output
+# channels, any stride / zero padding -- Inception-v3's Conv2d_1a (3x3, stride 2, no padding, 3 -> 32, BN
+# statistics in the epilogue) and VGG-16's first layer (3x3, stride 1, padding 1, 3 -> 64, bias + ReLU in
+# the epilogue).
 
 
 def stem3_eligible(conv: torch.nn.Conv2d, x: torch.Tensor) -> bool:
@@ -150,9 +153,11 @@ def stem3_eligible(conv: torch.nn.Conv2d, x: torch.Tensor) -> bool:
         return False
     kh, kw = conv.kernel_size
     sh, sw = conv.stride
+    if isinstance(conv.padding, str):
+        return False
     ph, pw = conv.padding
-    if not (conv.in_channels == 3 and conv.out_channels == 32 and kh <= 4 and kw <= 4 and sh == sw and sh >= 1
-            and ph < kh and pw < kw and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
+    if not (conv.in_channels == 3 and conv.out_channels in (32, 64) and kh <= 4 and kw <= 4 and sh == sw and sh >= 1
+            and ph < kh and pw < kw and conv.dilation == (1, 1) and conv.groups == 1
             and conv.padding_mode == "zeros"):
         return False
     return (x.shape[2] + 2 * ph - kh) // sh + 1 >= 1 and (x.shape[3] + 2 * pw - kw) // sw + 1 >= 1 and hip_available()
@@ -160,36 +165,55 @@ def stem3_eligible(conv: torch.nn.Conv2d, x: torch.Tensor) -> bool:
 
 class _Stem3Fn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, geo, stats):
+    def forward(ctx, x, w, geo, stats, bias, relu):
         H = hip()
         kh, kw, s, ph, pw = geo
         wb = w if w.dtype == torch.bfloat16 else w.to(torch.bfloat16)
         if not wb.is_contiguous(memory_format=torch.channels_last):
             wb = wb.contiguous(memory_format=torch.channels_last)
         # the f32 (or bf16) image is read as it is: no cast / pad pass
-        y = H.stem3_forward(x, H.stem3_pack_weight(wb), kh, kw, s, ph, pw, stats)
-        ctx.save_for_backward(x)
+        if bias is None and not relu:
+            y = H.stem3_forward(x, H.stem3_pack_weight(wb), kh, kw, s, ph, pw, stats)
+            ctx.save_for_backward(x)
+        else:
+            b32 = bias.float().contiguous() if bias is not None else None
+            y = H.stem3_forward(x, H.stem3_pack_weight(wb), kh, kw, s, ph, pw, stats, b32, relu)
+            ctx.save_for_backward(x, y)  # y: the ReLU gate of the backward
         ctx.geo = geo
         ctx.wdtype = w.dtype
+        ctx.epi = (bias is not None, bool(relu))
+        ctx.bdtype = bias.dtype if bias is not None else None
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        (x,) = ctx.saved_tensors
-        if not ctx.needs_input_grad[1]:
-            return None, None, None, None
+        has_bias, relu = ctx.epi
+        x = ctx.saved_tensors[0]
+        need_dw = ctx.needs_input_grad[1]
+        need_db = has_bias and ctx.needs_input_grad[4]
+        if not (need_dw or need_db):
+            return None, None, None, None, None, None
         if not dy.is_contiguous(memory_format=torch.channels_last):
             dy = dy.contiguous(memory_format=torch.channels_last)
-        kh, kw, s, ph, pw = ctx.geo
-        dw = hip().stem3_wgrad(dy.to(torch.bfloat16), x, kh, kw, s, ph, pw, out_f32=ctx.wdtype == torch.float32)
-        if dw.dtype != ctx.wdtype:
-            dw = dw.to(ctx.wdtype)
-        return None, dw, None, None
+        dy = dy.to(torch.bfloat16)
+        db = None
+        if has_bias or relu:
+            # one pass: dy gated by y > 0 and its per-channel sum (the bias gradient)
+            dy, db = hip().bias_act_backward(dy, ctx.saved_tensors[1], relu)
+            db = db.to(ctx.bdtype) if need_db else None
+        dw = None
+        if need_dw:
+            kh, kw, s, ph, pw = ctx.geo
+            dw = hip().stem3_wgrad(dy, x, kh, kw, s, ph, pw, out_f32=ctx.wdtype == torch.float32)
+            if dw.dtype != ctx.wdtype:
+                dw = dw.to(ctx.wdtype)
+        return None, dw, None, None, db, None
 
 
-def stem3_conv(conv: torch.nn.Conv2d, x: torch.Tensor, w: torch.Tensor,
-               stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+def stem3_conv(conv: torch.nn.Conv2d, x: torch.Tensor, w: torch.Tensor, stats: Optional[torch.Tensor] = None,
+               bias: Optional[torch.Tensor] = None, relu: bool = False) -> torch.Tensor:
     """``conv(x)`` with ``w`` (the bf16 shadow of ``conv.weight`` or the weight) on stem3.hip ->
-    bf16 [N, 32, OH, OW] channels_last; ``stats``: the following BN's f64 slotted sums workspace."""
+    bf16 [N, 32 | 64, OH, OW] channels_last; ``stats``: the following BN's f64 slotted sums workspace;
+    ``bias`` (+ ``relu``): ``relu(conv(x) + bias)``, the bias added in f32 before the one rounding."""
     geo = (conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.padding[0], conv.padding[1])
-    return _Stem3Fn.apply(x, w, geo, stats)
+    return _Stem3Fn.apply(x, w, geo, stats, bias, relu)

@@ -7,7 +7,9 @@ forward and a gate + bias-reduce pass over its output gradient in backward (``_B
 backward knows that the gradient of layer L's ReLU output is consumed only by layer L's
 bias/ReLU, so it is produced already gated:
 
-  forward   layer 0: library conv of the image + the in-place bias+ReLU pass (3 channels);
+  forward   layer 0: ``hip.stem3_forward(..., bias, relu)`` straight from the channels_last f32 / bf16
+            image -- relu(conv + b) in the MFMA epilogue, no bf16 image copy (else, e.g. ``KUNGFU_STEM=0``
+            or an NCHW image: library conv of the image + the in-place bias+ReLU pass);
             layers 1..12: ``hip.conv(..., bias=b)`` -- relu(conv + b) in the MFMA epilogue;
             pools: ``hip.maxpool2x2_forward``.
   backward  pool after layer L: ``maxpool2x2_backward(gate_stats=...)`` gathers, gates by the
@@ -15,7 +17,8 @@ bias/ReLU, so it is produced already gated:
             conv L+1 directly after layer L: its data gradient ``hip.conv(..., gate=True)``
             gates by layer L's output in the epilogue and sums the bias gradient there;
             weight gradients: ``ops.conv.wgrad`` (the row-image 3x3 kernel for <= 128
-            channels, the tap-tiled split-K kernel above; MIOpen for the 3-channel image).
+            channels, the tap-tiled split-K kernel above; ``hip.stem3_wgrad`` for the 3-channel image,
+            MIOpen where layer 0 is not on stem3).
 
 The bias gradients land in one zeroed f64 workspace (kStatSlots x 2 x C per layer, slot 0 row
 used) and are folded per layer.  Numerics match the layered path: the same bf16 conv outputs
@@ -36,21 +39,29 @@ from .._lib import buf_ok, hip, hip_available
 from .. import knobs
 
 _ENABLED = knobs.get("KUNGFU_VGG_FUSED") != "0"
+# The 3 -> 64 first layer on stem3.hip (forward with bias + ReLU in the epilogue, weight gradient) when the
+# image is eligible (ops.stem.stem3_eligible; KUNGFU_STEM=0 turns it off with the other image stems).
+STEM3 = True
 
 _CL = torch.channels_last
 
 
 class _FeaturesFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, pool_after: Tuple[bool, ...], *wb):
+    def forward(ctx, x, pool_after: Tuple[bool, ...], stem3: bool, *wb):
         H = hip()
         ws, bs = wb[0::2], wb[1::2]
         n = len(pool_after)
-        x0 = x.to(torch.bfloat16).contiguous(memory_format=_CL)  # what autocast hands the first conv
-        inputs: List[torch.Tensor] = [x0]
         pooled_src: List[torch.Tensor] = []  # ReLU outputs that feed a pool (the pool's x)
-        y = F.conv2d(x0, ws[0], None, 1, 1).contiguous(memory_format=_CL)
-        H.bias_act_forward_(y, bs[0].float().contiguous(), True)
+        if stem3:
+            # relu(conv(x) + b0) in one launch straight from the image (f32 or bf16, read as it is)
+            x0 = x
+            y = H.stem3_forward(x, H.stem3_pack_weight(ws[0]), 3, 3, 1, 1, 1, None, bs[0].float().contiguous(), True)
+        else:
+            x0 = x.to(torch.bfloat16).contiguous(memory_format=_CL)  # what autocast hands the first conv
+            y = F.conv2d(x0, ws[0], None, 1, 1).contiguous(memory_format=_CL)
+            H.bias_act_forward_(y, bs[0].float().contiguous(), True)
+        inputs: List[torch.Tensor] = [x0]
         for L in range(n):
             if L > 0:
                 y = H.conv(inputs[L], ws[L], 1, None, None, -1, bias=bs[L])
@@ -60,6 +71,7 @@ class _FeaturesFn(torch.autograd.Function):
             if L + 1 < n:
                 inputs.append(y)
         ctx.pool_after = pool_after
+        ctx.stem3 = stem3
         ctx.n_in = len(inputs)
         ctx.save_for_backward(*inputs, *pooled_src, *ws)
         ctx.bias_dtype = bs[0].dtype
@@ -93,14 +105,17 @@ class _FeaturesFn(torch.autograd.Function):
             else:
                 dz = g  # gated by conv L+1's data-gradient epilogue, bias sums in st[L]
             dbs[L] = st[L].view(slots, 2, couts[L])[:, 0].sum(0).to(ctx.bias_dtype)
-            dws[L] = wgrad(dz, inputs[L], ws[L], 1, 1)
+            if L == 0 and ctx.stem3:
+                dws[0] = H.stem3_wgrad(dz, inputs[0], 3, 3, 1, 1, 1)
+            else:
+                dws[L] = wgrad(dz, inputs[L], ws[L], 1, 1)
             if L > 0:
                 wf = H.conv3x3_flip_weight(ws[L])
                 if pool_after[L - 1]:
                     g = H.conv(dz, wf, 1)  # gradient of the pool output
                 else:  # gradient of layer L-1's ReLU output (= this conv's input), gated
                     g = H.conv(dz, wf, 1, st[L - 1], None, -1, bn_x=inputs[L], gate=True)
-        out = [None, None]
+        out = [None, None, None]
         for L in range(n):
             out += [dws[L], dbs[L]]
         return tuple(out)
@@ -166,4 +181,7 @@ class FusedVGGFeatures(nn.Sequential):
             if b.dtype != torch.bfloat16:
                 b = b.to(torch.bfloat16)
             wb += [w.contiguous(memory_format=_CL), b.contiguous()]
-        return _FeaturesFn.apply(x, pool_after, *wb)
+        from .stem import stem3_eligible
+
+        stem3 = STEM3 and stem3_eligible(convs[0], x)
+        return _FeaturesFn.apply(x, pool_after, stem3, *wb)
