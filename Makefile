@@ -44,7 +44,7 @@ BINS       := bin/kungfu-run bin/kungfu-config-server bin/kungfu-rrun bin/kungfu
 
 HIP_SRCS   := $(wildcard csrc/kernels/*.hip)
 HIP_OBJS   := $(patsubst csrc/kernels/%.hip,$(BUILD)/hip/%.o,$(HIP_SRCS))
-HIP_BIND   := $(BUILD)/hip/bindings.o
+HIP_BIND   := $(patsubst csrc/kernels/%.cpp,$(BUILD)/hip/%.o,csrc/kernels/bindings.cpp $(wildcard csrc/kernels/bind_*.cpp))
 HIP_MOD    := kungfu_amd/_hip$(PYEXT)
 HIPFLAGS   := -std=c++17 -O3 -fPIC --offload-arch=$(ARCH) -Icsrc/include -D__HIP_PLATFORM_AMD__ \
               -ffp-contract=fast -munsafe-fp-atomics -Wno-unused-result $(EXTRA_HIPFLAGS)
@@ -109,7 +109,7 @@ $(BUILD)/hip/%.o: csrc/kernels/%.hip $(wildcard csrc/kernels/*.hpp)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(HIP_BIND): csrc/kernels/bindings.cpp $(wildcard csrc/kernels/*.hpp)
+$(HIP_BIND): $(BUILD)/hip/%.o: csrc/kernels/%.cpp $(wildcard csrc/kernels/*.hpp)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) $(TORCH_INC) -DTORCH_EXTENSION_NAME=_hip -DUSE_ROCM -fvisibility=hidden -c $< -o $@
 

@@ -21,8 +21,8 @@
 // 16 rows a ds_read_b128 touches spread over 8 chunk positions.  Blocks are
 // remapped XCD-contiguously (consecutive tiles share input halo rows in L2).
 //
-// The same kernel computes the stride-1 data gradient: dx = conv3x3(dy, w')
-// with w'[ci, kh, kw, co] = w[co, 2-kh, 2-kw, ci] (conv3x3_flip_weight).
+// The same kernel computes the stride-1 data gradient: dx = conv(dy, w')
+// with w'[ci, kh, kw, co] = w[co, 2-kh, 2-kw, ci] (conv_flip_weight).
 #include "conv_kernel.hpp"
 
 namespace kfk {
@@ -101,12 +101,8 @@ void launch_conv_flip_multi(const FlipTable &tab_in, hipStream_t s) {
 
 // Channel / stride predicates only: the caller also checks that x and w stay below 2 GiB
 // (buffer-resource staging, check_buf_extent; kungfu_amd._lib.buf_ok on the Python side).
-bool conv3x3_supported(int Cin, int Cout, int stride) {
-    return Cin % 64 == 0 && Cout % 64 == 0 && (stride == 1 || stride == 2) && Cin >= 64;
-}
-
 bool conv_supported(int Cin, int Cout, int ks, int stride) {
-    return (ks == 1 || ks == 3) && conv3x3_supported(Cin, Cout, stride);
+    return (ks == 1 || ks == 3) && Cin % 64 == 0 && Cout % 64 == 0 && (stride == 1 || stride == 2) && Cin >= 64;
 }
 
 // KUNGFU_CONV_TILE_RULES: 1 = the round-2 tile defaults, 2 (default) = the round-3 re-measured ones
@@ -152,7 +148,7 @@ void check_buf_extent(const Geo &g) {
 }
 
 
-int conv3x3_variants() { return 12; }
+int conv_variants() { return 12; }
 
 void launch_conv(const uint16_t *x, const uint16_t *w, uint16_t *y, int N, int H, int W, int Cin, int Cout, int ks,
                  int stride, const EpiArgs &ea, int epi, hipStream_t s, int variant) {
@@ -175,11 +171,6 @@ void launch_conv(const uint16_t *x, const uint16_t *w, uint16_t *y, int N, int H
 // (the gradient of a BN+ReLU output: sum dz, sum dz*x into the stats slots) epilogue, 256x128 / 8 waves when
 // Cout % 128 == 0, else 256x64.
 
-void launch_conv3x3(const uint16_t *x, const uint16_t *w, uint16_t *y, int N, int H, int W, int Cin, int Cout,
-                    int stride, hipStream_t s, int variant) {
-    launch_conv(x, w, y, N, H, W, Cin, Cout, 3, stride, EpiArgs{}, 0, s, variant);
-}
-
 void launch_conv_flip_weight(const uint16_t *w, uint16_t *wt, int Cout, int Cin, int ks, hipStream_t s) {
     launch_conv_flip_weight_taps(w, wt, Cout, Cin, ks * ks, s);
 }
@@ -189,10 +180,6 @@ void launch_conv_flip_weight_taps(const uint16_t *w, uint16_t *wt, int Cout, int
     int grid = static_cast<int>((n + 255) / 256);
     if (grid > 4096) grid = 4096;
     conv_flip_kernel<<<grid, 256, 0, s>>>(w, wt, Cout, Cin, taps);
-}
-
-void launch_conv3x3_flip_weight(const uint16_t *w, uint16_t *wt, int Cout, int Cin, hipStream_t s) {
-    launch_conv_flip_weight(w, wt, Cout, Cin, 3, s);
 }
 
 

@@ -21,8 +21,8 @@
 // 16 rows a ds_read_b128 touches spread over 8 chunk positions.  Blocks are
 // remapped XCD-contiguously (consecutive tiles share input halo rows in L2).
 //
-// The same kernel computes the stride-1 data gradient: dx = conv3x3(dy, w')
-// with w'[ci, kh, kw, co] = w[co, 2-kh, 2-kw, ci] (conv3x3_flip_weight).
+// The same kernel computes the stride-1 data gradient: dx = conv(dy, w')
+// with w'[ci, kh, kw, co] = w[co, 2-kh, 2-kw, ci] (conv_flip_weight).
 //
 // This header holds the kernel template and its launch helpers; the instantiations are spread over
 // conv.hip (dispatch, weight flips), conv_k1.hip / conv_k3.hip (square windows), conv_rect.hip,

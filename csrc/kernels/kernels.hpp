@@ -177,14 +177,8 @@ struct GradAccTable {
 int grad_accumulate_blocks(int64_t numel);
 void launch_grad_accumulate(const GradAccTable &tab, float *flat, hipStream_t s);
 
-// 3x3 convolution, pad 1, stride 1|2, NHWC bf16 (x [N,H,W,Cin], w [Cout,3,3,Cin],
-// y [N,OH,OW,Cout]) as an MFMA implicit GEMM (conv.hip).  Cin, Cout multiples of 64.
-bool conv3x3_supported(int Cin, int Cout, int stride);
-// variant: tile/pipeline choice (-1 = default for the shape; 0..conv3x3_variants()-1 for tuning).
-void launch_conv3x3(const uint16_t *x, const uint16_t *w, uint16_t *y, int N, int H, int W, int Cin, int Cout,
-                    int stride, hipStream_t s, int variant = -1);
-int conv3x3_variants();
-// General KS x KS (KS = 1 or 3, pad (KS-1)/2) convolution with fused epilogues:
+// KS x KS (KS = 1 or 3, pad (KS-1)/2) convolution, stride 1|2, NHWC bf16 (x [N,H,W,Cin], w [Cout,KS,KS,Cin],
+// y [N,OH,OW,Cout]) as an MFMA implicit GEMM (conv.hip), Cin, Cout multiples of 64, with fused epilogues:
 // stats != nullptr: f64 atomics of per-output-channel sum / sum of squares of the bf16
 // outputs into stats[0..K) / stats[K..2K) (the caller zeroes them; bn_stats_from_sums
 // consumes and re-zeroes them); accumulate: y += conv(x, w) instead of y = conv(x, w).
@@ -192,6 +186,8 @@ int conv3x3_variants();
 // keeping atomic contention per address low); bn_forward(sums=...) folds the slots.
 constexpr int kStatSlots = 16;
 bool conv_supported(int Cin, int Cout, int ks, int stride);
+// variant: tile/pipeline choice (-1 = default for the shape; 0..conv_variants()-1 for tuning).
+int conv_variants();
 // kEpiBiasRelu: y = relu(conv + bias) (bf16 bias, VGG's conv+bias+ReLU in the conv's epilogue);
 // kEpiGate: the output is the gradient of a ReLU output ea.bx: y = conv * (bx > 0) (NaN in bx
 // passes, like torch.relu's backward) and stats[slot][0][c] += sum(y) (that layer's bias gradient).
@@ -259,8 +255,6 @@ void launch_conv_flip_multi(const FlipTable &tab, hipStream_t s);
 void launch_conv_flip_weight(const uint16_t *w, uint16_t *wt, int Cout, int Cin, int ks, hipStream_t s);
 // Any KH x KW window: the flattened tap index is reversed (taps = KH*KW).
 void launch_conv_flip_weight_taps(const uint16_t *w, uint16_t *wt, int Cout, int Cin, int taps, hipStream_t s);
-// wt[ci,kh,kw,co] = w[co,2-kh,2-kw,ci]: stride-1 data gradient = conv3x3(dy, wt).
-void launch_conv3x3_flip_weight(const uint16_t *w, uint16_t *wt, int Cout, int Cin, hipStream_t s);
 
 // Weight gradient of the KS x KS (pad (KS-1)/2, stride 1|2) NHWC convolution as a split-K
 // MFMA GEMM (conv_wgrad.hip): dw[co, kh, kw, ci] = sum_p dy[p, co] * x[pix(p, kh, kw), ci].

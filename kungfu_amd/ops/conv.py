@@ -3,9 +3,10 @@
 ``conv3x3(x, w, stride)`` computes ``F.conv2d(x, w, stride=stride, padding=1)`` for NHWC
 (channels_last) bf16 tensors with Cin, Cout multiples of 64:
 
-* forward: ``_hip.conv3x3`` (stride 1 or 2);
+* forward: ``_hip.conv`` (stride 1 or 2);
 * data gradient, stride 1: the same kernel on the flipped/transposed weights
-  (``dx = conv3x3(dy, w')``, ``w'[ci,co,kh,kw] = w[co,ci,2-kh,2-kw]``);
+  (``dx = _hip.conv(dy, w')``, ``w' = _hip.conv_flip_weight(w)``:
+  ``w'[ci,co,kh,kw] = w[co,ci,2-kh,2-kw]``);
   stride 2: MIOpen (``aten.convolution_backward``);
 * weight gradient: the split-K MFMA kernel (csrc/kernels/conv_wgrad.hip, ``wgrad`` below,
   also used by the fused bottleneck blocks) for 1x1 / 3x3, stride 1 / 2.
@@ -93,7 +94,7 @@ def eligible(x: torch.Tensor, w: torch.Tensor, stride, padding, dilation, groups
         return False
     if not hip_available() or not buf_ok(x.numel(), w.numel()):
         return False
-    return hip().conv3x3_supported(int(x.shape[1]), int(w.shape[0]), int(st))
+    return hip().conv_supported(int(x.shape[1]), int(w.shape[0]), 3, int(st))
 
 
 class _Conv3x3Fn(torch.autograd.Function):
@@ -101,7 +102,7 @@ class _Conv3x3Fn(torch.autograd.Function):
     def forward(ctx, x, w, stride):
         ctx.save_for_backward(x, w)
         ctx.stride = stride
-        return hip().conv3x3(x, w, stride)
+        return hip().conv(x, w, stride)
 
     @staticmethod
     def backward(ctx, dy):
@@ -112,7 +113,7 @@ class _Conv3x3Fn(torch.autograd.Function):
         need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         dx = dw = None
         if need_dx and s == 1:
-            dx = hip().conv3x3(dy, hip().conv3x3_flip_weight(w), 1)
+            dx = hip().conv(dy, hip().conv_flip_weight(w), 1)
             need_dx = False
         if need_dw:
             dw = wgrad(dy, x, w, s, 1)

@@ -110,7 +110,7 @@ class _FeaturesFn(torch.autograd.Function):
             else:
                 dws[L] = wgrad(dz, inputs[L], ws[L], 1, 1)
             if L > 0:
-                wf = H.conv3x3_flip_weight(ws[L])
+                wf = H.conv_flip_weight(ws[L])
                 if pool_after[L - 1]:
                     g = H.conv(dz, wf, 1)  # gradient of the pool output
                 else:  # gradient of layer L-1's ReLU output (= this conv's input), gated
@@ -161,7 +161,7 @@ class FusedVGGFeatures(nn.Sequential):
         for i, c in enumerate(convs):
             if c.kernel_size != (3, 3) or c.stride != (1, 1) or c.padding != (1, 1) or c.groups != 1 or c.bias is None:
                 return False
-            if i > 0 and not H.conv3x3_supported(c.in_channels, c.out_channels, 1):
+            if i > 0 and not H.conv_supported(c.in_channels, c.out_channels, 3, 1):
                 return False
             if not H.bias_act_supported(c.out_channels):
                 return False

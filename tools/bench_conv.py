@@ -91,7 +91,7 @@ for Hh, C, K, ks, s in SHAPES:
     fl = 2.0 * N * OH * OH * K * C * ks * ks
     line += " (%.2f TB/s %.0f TF/s)" % (byt / t_o / 1e6, fl / t_o / 1e6)
     vs = []
-    for v in range(H_.conv3x3_variants()):
+    for v in range(H_.conv_variants()):
         if v in (0, 1) and K % 128:
             continue
         try:

@@ -43,7 +43,7 @@ def main():
     a = ap.parse_args()
     N = a.batch
     shapes = SHAPES if a.shape < 0 else [SHAPES[a.shape]]
-    variants = list(range(H_.conv3x3_variants())) if a.variant is None else [a.variant]
+    variants = list(range(H_.conv_variants())) if a.variant is None else [a.variant]
     for Hh, C, K in shapes:
         x = cl(torch.randn(N, C, Hh, Hh, device="cuda")).bfloat16()
         w = cl(torch.randn(K, C, 3, 3, device="cuda") * 0.05).bfloat16()
