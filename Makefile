@@ -113,7 +113,12 @@ $(HIP_BIND): $(BUILD)/hip/%.o: csrc/kernels/%.cpp $(wildcard csrc/kernels/*.hpp)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) $(TORCH_INC) -DTORCH_EXTENSION_NAME=_hip -DUSE_ROCM -fvisibility=hidden -c $< -o $@
 
-$(HIP_MOD): $(HIP_OBJS) $(HIP_BIND)
+# the weight-gradient planner: host-only C++ (also built stand-alone as build/wgrad_plan_dump below)
+$(BUILD)/hip/wgrad_plan.o: csrc/kernels/wgrad_plan.cpp csrc/kernels/wgrad_plan.hpp
+	@mkdir -p $(dir $@)
+	$(CXX) $(CXXFLAGS) -c $< -o $@
+
+$(HIP_MOD): $(HIP_OBJS) $(HIP_BIND) $(BUILD)/hip/wgrad_plan.o
 	$(HIPCC) -shared --offload-arch=$(ARCH) -o $@ $^ $(TORCH_LIBS) -lrccl -L/opt/rocm/lib
 
 clean:
@@ -134,6 +139,14 @@ build/native_test_asan: $(NT_SRCS) $(wildcard csrc/include/kungfu/*.hpp)
 build/native_test_tsan: $(NT_SRCS) $(wildcard csrc/include/kungfu/*.hpp)
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) -O1 -g -fsanitize=thread -o $@ $(NT_SRCS) $(LDFLAGS)
+# the weight-gradient planner over a list of shapes (tests/test_wgrad_plan.py)
+WP_SRCS := tests/native/wgrad_plan_dump.cpp csrc/kernels/wgrad_plan.cpp
+build/wgrad_plan_dump: $(WP_SRCS) csrc/kernels/wgrad_plan.hpp
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) -Icsrc/kernels -g -o $@ $(WP_SRCS)
+build/wgrad_plan_dump_asan: $(WP_SRCS) csrc/kernels/wgrad_plan.hpp
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) -Icsrc/kernels -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -o $@ $(WP_SRCS)
 native-test: build/native_test
 	./build/native_test
 native-test-asan: build/native_test_asan

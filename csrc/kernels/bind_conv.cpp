@@ -1,6 +1,8 @@
 // The MFMA implicit-GEMM family: conv, conv_rect, their data / weight gradients, the weight flips and gemm.
 #include "bind_util.hpp"
 
+#include <array>
+#include <optional>
 #include <vector>
 
 using namespace kfb;
@@ -169,6 +171,27 @@ at::Tensor conv_dgrad_s2(at::Tensor dy, at::Tensor wt, int64_t ks, OptTensor sta
     return dx;
 }
 
+// The shared tail of the two weight-gradient bindings: dy against the shape, extents, allocate, launch.
+at::Tensor wgrad_launch(const char *op, const at::Tensor &dy, const at::Tensor &x, const kfk::WgradPlan &plan,
+                        OptTensor out, bool accumulate, bool atomics) {
+    const kfk::WgradShape &sh = plan.shape;
+    const bool f32 = has(out) && out->scalar_type() == at::kFloat;
+    c10::DeviceGuard gd(x.device());
+    auto dw = out_or_empty(out, {sh.Cout, sh.Cin, sh.kh, sh.kw},
+                           x.options().dtype(f32 ? at::kFloat : at::kBFloat16).memory_format(kCL), op).first;
+    at::Tensor ws;
+    if (plan.ws_floats > 0) ws = at::empty({plan.ws_floats}, x.options().dtype(at::kFloat));
+    kfk::launch_conv_wgrad(bf16(dy), bf16(x), dw.data_ptr(), plan.ws_floats > 0 ? ws.data_ptr<float>() : nullptr, plan,
+                           f32, accumulate, stream_of(x, 0), atomics);
+    return dw;
+}
+
+void wgrad_check(const char *op, const at::Tensor &dy, const at::Tensor &x, const kfk::WgradShape &sh) {
+    check_cl4(dy, op, "dy", x.device(), {sh.N, sh.Cout, sh.OH(), sh.OW()});
+    check_extent32(op, "x", {sh.N, sh.H, sh.W, sh.Cin});
+    check_extent32(op, "dy", {sh.N, sh.OH(), sh.OW(), sh.Cout});
+}
+
 // Weight gradient of conv(x, w, stride, pad (ks-1)/2): dw [Cout, Cin, ks, ks] channels_last
 // (memory [Cout][ks][ks][Cin]).  out: bf16 or f32 destination of that shape/layout (written,
 // or added to with accumulate); otherwise a new bf16 tensor.  variant / splits: -1 = planner.
@@ -176,28 +199,16 @@ at::Tensor conv_wgrad(at::Tensor dy, at::Tensor x, int64_t ks, int64_t stride, O
                       int64_t variant, int64_t splits, bool atomics) {
     const char *op = "conv_wgrad";
     check_cl4(x, op, "x", kAnyGpu);
-    const Dev dev = x.device();
-    check_cl4(dy, op, "dy", dev);
+    check_cl4(dy, op, "dy", Dev(x.device()));
     const auto [N, C, H, W] = dims4(x, op, "x");
-    const int K = narrow(dy.size(1), op, "dy"), k = narrow(ks, op, "ks"), st = narrow(stride, op, "stride");
-    TORCH_CHECK(kfk::conv_wgrad_supported(C, K, k, st), "conv_wgrad: unsupported channels/kernel/stride");
-    const int pad = (k - 1) / 2;
-    const int OH = (H + 2 * pad - k) / st + 1, OW = (W + 2 * pad - k) / st + 1;
-    check_cl4(dy, op, "dy", dev, {N, K, OH, OW});
-    check_extent32(op, "x", {N, H, W, C});
-    check_extent32(op, "dy", {N, OH, OW, K});
+    const auto sh = kfk::wgrad_square_shape(N, H, W, C, narrow(dy.size(1), op, "dy"), narrow(ks, op, "ks"),
+                                            narrow(stride, op, "stride"));
+    TORCH_CHECK(kfk::conv_wgrad_supported(sh.Cin, sh.Cout, sh.kh, sh.stride), "conv_wgrad: unsupported channels/kernel/stride");
+    wgrad_check(op, dy, x, sh);
     TORCH_CHECK(has(out) || !accumulate, "conv_wgrad: accumulate needs out");
-    const bool f32 = has(out) && out->scalar_type() == at::kFloat;
-    const auto plan = kfk::conv_wgrad_plan(N, H, W, C, K, k, st, narrow(variant, op, "variant"),
+    const auto plan = kfk::conv_wgrad_plan(sh, kfk::WgradFamily::Square, narrow(variant, op, "variant"),
                                            narrow(splits, op, "splits"));
-    c10::DeviceGuard gd(x.device());
-    auto dw = out_or_empty(out, {K, C, k, k}, x.options().dtype(f32 ? at::kFloat : at::kBFloat16).memory_format(kCL),
-                           op).first;
-    at::Tensor ws;
-    if (plan.ws_floats > 0) ws = at::empty({plan.ws_floats}, x.options().dtype(at::kFloat));
-    kfk::launch_conv_wgrad(bf16(dy), bf16(x), dw.data_ptr(), plan.ws_floats > 0 ? ws.data_ptr<float>() : nullptr, N, H,
-                           W, C, K, k, st, plan, f32, accumulate, stream_of(x, 0), atomics);
-    return dw;
+    return wgrad_launch(op, dy, x, plan, out, accumulate, atomics);
 }
 
 // Weight gradient of a KH x KW convolution with zero padding (ph, pw): dw [Cout, Cin, KH, KW]
@@ -206,25 +217,16 @@ at::Tensor conv_wgrad_rect(at::Tensor dy, at::Tensor x, int64_t kh, int64_t kw, 
                            int64_t variant) {
     const char *op = "conv_wgrad_rect";
     check_cl4(x, op, "x", kAnyGpu);
-    const Dev dev = x.device();
-    check_cl4(dy, op, "dy", dev);
+    check_cl4(dy, op, "dy", Dev(x.device()));
     const auto [N, C, H, W] = dims4(x, op, "x");
-    const int K = narrow(dy.size(1), op, "dy"), st = narrow(stride, op, "stride");
-    const int KH = narrow(kh, op, "kh"), KW = narrow(kw, op, "kw"), PH = narrow(ph, op, "ph"), PW = narrow(pw, op, "pw");
-    TORCH_CHECK(kfk::conv_wgrad_rect_supported(C, K, KH, KW, st) && PH >= 0 && PW >= 0 && PH < KH && PW < KW,
+    const kfk::WgradShape sh{N, H, W, C, narrow(dy.size(1), op, "dy"), narrow(kh, op, "kh"), narrow(kw, op, "kw"),
+                             narrow(ph, op, "ph"), narrow(pw, op, "pw"), narrow(stride, op, "stride")};
+    TORCH_CHECK(kfk::conv_wgrad_rect_supported(sh.Cin, sh.Cout, sh.kh, sh.kw, sh.stride) && sh.ph >= 0 && sh.pw >= 0 &&
+                    sh.ph < sh.kh && sh.pw < sh.kw,
                 "conv_wgrad_rect: unsupported channels/window/stride/padding");
-    const int OH = (H + 2 * PH - KH) / st + 1, OW = (W + 2 * PW - KW) / st + 1;
-    check_cl4(dy, op, "dy", dev, {N, K, OH, OW});
-    check_extent32(op, "x", {N, H, W, C});
-    check_extent32(op, "dy", {N, OH, OW, K});
-    const auto plan = kfk::conv_wgrad_rect_plan(N, H, W, C, K, KH, KW, PH, PW, st, narrow(variant, op, "variant"));
-    c10::DeviceGuard gd(x.device());
-    auto dw = at::empty({K, C, KH, KW}, x.options().memory_format(kCL));
-    at::Tensor ws;
-    if (plan.ws_floats > 0) ws = at::empty({plan.ws_floats}, x.options().dtype(at::kFloat));
-    kfk::launch_conv_wgrad_rect(bf16(dy), bf16(x), dw.data_ptr(), plan.ws_floats > 0 ? ws.data_ptr<float>() : nullptr, N,
-                                H, W, C, K, KH, KW, PH, PW, st, plan, false, false, stream_of(x, 0));
-    return dw;
+    wgrad_check(op, dy, x, sh);
+    const auto plan = kfk::conv_wgrad_plan(sh, kfk::WgradFamily::Rect, narrow(variant, op, "variant"));
+    return wgrad_launch(op, dy, x, plan, OptTensor(), false, true);
 }
 
 // [Cout, Cin, KS, KS] channels_last -> flipped/transposed [Cin, Cout, KS, KS] channels_last
@@ -333,24 +335,56 @@ void bind_conv(py::module_ &m) {
     m.def("conv_wgrad_rect", &conv_wgrad_rect, "weight gradient of a KH x KW padded NHWC bf16 convolution "
           "(split-K MFMA GEMM, any channel count % 8)", py::arg("dy"), py::arg("x"), py::arg("kh"), py::arg("kw"),
           py::arg("stride") = 1, py::arg("ph") = 0, py::arg("pw") = 0, py::arg("variant") = -1);
-    m.def("conv_wgrad_rect_supported", &kfk::conv_wgrad_rect_supported);
-    m.def("conv_wgrad_rows_rect_auto", &kfk::conv_wgrad_rows_rect_auto, "the row-image weight-gradient variant "
-          "conv_wgrad_rect(..., 13) picks for this shape (args: N, H, W, Cin, Cout, kh, kw, ph, pw, stride)");
-    m.def("conv_wgrad_rows_rect_supported", &kfk::conv_wgrad_rows_rect_supported, "row-image weight-gradient kernel "
-          "covers this stride-1 window (args: N, H, W, Cin, Cout, kh, kw, ph, pw, stride)");
     m.def("conv_wgrad", &conv_wgrad, "weight gradient of the 1x1/3x3 NHWC bf16 convolution (split-K MFMA GEMM)",
           py::arg("dy"), py::arg("x"), py::arg("ks"), py::arg("stride") = 1, py::arg("out") = py::none(),
           py::arg("accumulate") = false, py::arg("variant") = -1, py::arg("splits") = -1,
           py::arg("atomics") = true);
+    // ---- the weight-gradient planner (wgrad_plan.hpp): host-only queries
     m.def("conv_wgrad_supported", &kfk::conv_wgrad_supported);
-    m.def("conv_wgrad_variants", &kfk::conv_wgrad_variants);
-    m.def("conv_wgrad_max_pixels", &kfk::conv_wgrad_max_pixels, py::arg("N"), py::arg("H"), py::arg("W"),
-          py::arg("Cin"), py::arg("Cout"), py::arg("ks"), py::arg("stride"));
-    m.def("conv_wgrad_plan", [](int N, int H, int W, int Cin, int Cout, int ks, int stride, int variant, int splits) {
-        const auto p = kfk::conv_wgrad_plan(N, H, W, Cin, Cout, ks, stride, variant, splits);
-        return py::make_tuple(p.variant, p.splits, p.kps, p.ws_floats);
-    }, py::arg("N"), py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"), py::arg("ks"), py::arg("stride"),
-          py::arg("variant") = -1, py::arg("splits") = -1);
+    m.def("conv_wgrad_rect_supported", &kfk::conv_wgrad_rect_supported);
+    m.def("conv_wgrad_variants", [] { return kfk::kWgradSquareVariants; });
+    m.def("conv_wgrad_rows_rect_supported", [](int N, int H, int W, int Cin, int Cout, int kh, int kw, int ph, int pw,
+                                               int stride) {
+        return kfk::conv_wgrad_rows_rect_supported({N, H, W, Cin, Cout, kh, kw, ph, pw, stride});
+    }, "a row-image weight-gradient kernel covers this multi-tap window (args: N, H, W, Cin, Cout, kh, kw, ph, pw, stride)");
+    m.def("conv_wgrad_rows_rect_auto", [](int N, int H, int W, int Cin, int Cout, int kh, int kw, int ph, int pw,
+                                          int stride) {
+        return kfk::conv_wgrad_rows_rect_auto({N, H, W, Cin, Cout, kh, kw, ph, pw, stride});
+    }, "the row-image variant conv_wgrad_rect(..., WGRAD_ROWS_AUTO) picks for this shape (args: N, H, W, Cin, Cout, kh, "
+       "kw, ph, pw, stride)");
+    m.def("conv_wgrad_plan", [](int N, int H, int W, int Cin, int Cout, int ks, int stride, int variant, int splits,
+                                std::optional<std::array<int, 4>> window) {
+        const auto p = window ? kfk::conv_wgrad_plan({N, H, W, Cin, Cout, (*window)[0], (*window)[1], (*window)[2],
+                                                      (*window)[3], stride}, kfk::WgradFamily::Rect, variant)
+                              : kfk::conv_wgrad_plan(kfk::wgrad_square_shape(N, H, W, Cin, Cout, ks, stride),
+                                                     kfk::WgradFamily::Square, variant, splits);
+        return py::make_tuple(p.variant, p.splits, p.kps, p.ws_floats, kfk::wgrad_kernel_name(p.kernel));
+    }, "(variant, splits, kps, ws_floats, kernel) of conv_wgrad's plan, or with window = (kh, kw, ph, pw) of "
+       "conv_wgrad_rect's (ks and splits are then unused)", py::arg("N"), py::arg("H"), py::arg("W"), py::arg("Cin"),
+          py::arg("Cout"), py::arg("ks"), py::arg("stride"), py::arg("variant") = -1, py::arg("splits") = -1,
+          py::arg("window") = py::none());
+    m.def("conv_wgrad_route", [](int N, int H, int W, int Cin, int Cout, int kh, int kw, int ph, int pw, int stride) {
+        const auto r = kfk::conv_wgrad_route({N, H, W, Cin, Cout, kh, kw, ph, pw, stride});
+        return py::make_tuple(kfk::wgrad_route_name(r.route), r.variant, r.max_pixels);
+    }, "(route, variant, max_pixels): 'library', or the family ('square': conv_wgrad, 'rect': conv_wgrad_rect) and the "
+       "variant code that take this convolution's weight gradient, and the output pixels one launch handles",
+          py::arg("N"), py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"), py::arg("kh"), py::arg("kw"),
+          py::arg("ph"), py::arg("pw"), py::arg("stride"));
+    m.attr("WGRAD_AUTO") = static_cast<int>(kfk::kWgradAuto);
+    m.attr("WGRAD_TILE_128x128") = static_cast<int>(kfk::kWgradTile128x128);
+    m.attr("WGRAD_TILE_128x64") = static_cast<int>(kfk::kWgradTile128x64);
+    m.attr("WGRAD_TILE_64x128") = static_cast<int>(kfk::kWgradTile64x128);
+    m.attr("WGRAD_TILE_64x64") = static_cast<int>(kfk::kWgradTile64x64);
+    m.attr("WGRAD_TILE_256x128") = static_cast<int>(kfk::kWgradTile256x128);
+    m.attr("WGRAD_TILE_128x256") = static_cast<int>(kfk::kWgradTile128x256);
+    m.attr("WGRAD_ROWS") = static_cast<int>(kfk::kWgradRows);
+    m.attr("WGRAD_TILE_256x256") = static_cast<int>(kfk::kWgradTile256x256);
+    m.attr("WGRAD_RING_32x2") = static_cast<int>(kfk::kWgradRing32x2);
+    m.attr("WGRAD_RING_32x3") = static_cast<int>(kfk::kWgradRing32x3);
+    m.attr("WGRAD_RING_32x4") = static_cast<int>(kfk::kWgradRing32x4);
+    m.attr("WGRAD_RING_64x3") = static_cast<int>(kfk::kWgradRing64x3);
+    m.attr("WGRAD_RING_64x4") = static_cast<int>(kfk::kWgradRing64x4);
+    m.attr("WGRAD_ROWS_AUTO") = static_cast<int>(kfk::kWgradRowsAuto);
     m.def("conv_flip_weight", &conv_flip_weight, "w[co,ci,kh,kw] -> w[ci,co,KS-1-kh,KS-1-kw] (data-gradient weights)");
     m.def("conv_flip_weights", &conv_flip_weights, "multi-tensor conv_flip_weight into preallocated outputs");
 }

@@ -29,11 +29,13 @@
 // Reference parity: the reference has no kernels of its own; it trains
 // tf.keras.applications ResNet-50 with TF's stock convolutions
 // (benchmarks/system/benchmark_kungfu.py:96).
+//
+// Which of these kernels a shape gets, on which tile and with how many splits, is decided in
+// wgrad_plan.cpp (host-only); this file holds the kernels, whose geometry arguments (WGeo, RGeo,
+// RRGeo) that planner fills, and the one launcher that runs a plan.
 #include "common.hpp"
 #include "kernels.hpp"
 
-#include <algorithm>
-#include <cstdlib>
 #include <stdexcept>
 
 namespace kfk {
@@ -49,14 +51,6 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 constexpr int kBK = 64;  // pixels per K-step
-
-struct WGeo {
-    int N, H, W, C, OH, OW, K;
-    int P, HW;
-    uint64_t m_hw, m_ow;  // floor(p / d) = (p * m) >> 40, exact for p * d < 2^40
-    int mtiles, ntiles, taps, tiles, splits, kps;
-    int kwin, ph, pw;  // KS == 0 (any window): taps per kernel row and the zero padding
-};
 
 // Cache policy of the split-K kernel's LDS-DMA operand loads: non-temporal (aux = 2).  Measured
 // on the ResNet-50 step (r3h, tools/gpu_r3_ntconv.sh): +1 % with nt on both operands; the same
@@ -333,13 +327,6 @@ __global__ __launch_bounds__(64 * WM * WN) void wgrad_kernel(const uint16_t *__r
 //     is only an address offset -- every input pixel is staged once per segment.
 // 33-35 LDS-DMA pieces per K-step are spread over the 9 waves (4 each) against 32 MFMAs per
 // wave.  Partial tiles use wgrad_kernel's workspace order (reduced by wgrad_reduce_kernel).
-struct RGeo {
-    int N, H, W, C, K;
-    int L, R, spr, gpi, nseg;  // segment: L pixels per row, R rows; segments per row / per image
-    int XW, xrows, xpieces;    // input image: XW = L + 2 pixels per row, xrows rows, 1 KB pieces
-    int mtiles, ntiles, tiles, splits, kps;
-};
-
 template <int STAGES>
 __global__ __launch_bounds__(576) void wgrad_rows_kernel(const uint16_t *__restrict__ dy,
                                                          const uint16_t *__restrict__ x,
@@ -543,16 +530,6 @@ __global__ __launch_bounds__(576) void wgrad_rows_kernel(const uint16_t *__restr
 // 32 x 32 wave tile) -- CT 32 also writes its split partials in dw layout ([split][co][tap][ci],
 // exactly K * taps * C floats, no tile padding), summed by wgrad_dense_reduce_kernel.
 // Replaces MIOpen's igemm_wrw for these shapes (r2o_inception_wgrad.txt: 170-275 TF/s there).
-struct RRGeo {
-    int N, H, W, C, K, OH, OW;
-    int KH, KW, ph, pw, taps, tgroups;
-    int L, R, spr, gpi, nseg;
-    int XW, xrows, xpieces;
-    int mtiles, ntiles, tiles, splits, kps;
-    int stage;  // LDS bytes per ring stage: dy | image | 1 KB dummy
-    int S;      // stride (1, or 2 on the kRowsEx variants)
-};
-
 // s_waitcnt until at most n * (S - 2) loads of this wave are in flight (n = its loads per stage,
 // wave-uniform, 1..5): the oldest outstanding stage of an S-deep ring has landed
 template <int S>
@@ -906,92 +883,19 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float *__restri
     }
 }
 
-// Staggered staging issue in the row-image kernels (see wgrad_kernel), default on (same-box A/Bs:
-// Inception-v3 21.62 -> 21.45 ms/step, VGG-16 34.85 -> 34.62, ResNet-50 neutral);
-int rows_stagger(bool /*rect*/) { return 1; }
+// Staggered staging issue (see wgrad_kernel) is on in every row-image launch below (stagger = 1; same-box
+// A/Bs: Inception-v3 21.62 -> 21.45 ms/step, VGG-16 34.85 -> 34.62, ResNet-50 neutral).
 
-struct Tile {
-    int wm, wn, tn;  // waves (co, ci) and 16-channel ci blocks per wave
-    constexpr int bm() const { return 64 * wm; }
-    constexpr int bn() const { return 16 * tn * wn; }
-};
-// variant -> tile (co x ci): 0 128x128, 1 128x64, 2 64x128, 3 64x64, 4 256x128, 5 128x256,
-// 6 the row-image kernel (below), 7 256x256 (8 waves of 64x128: twice the MFMAs per staged byte)
-constexpr Tile kTiles[] = {{2, 2, 4}, {2, 1, 4}, {1, 2, 4}, {1, 1, 4}, {4, 2, 4}, {2, 4, 4}, {0, 0, 0}, {4, 2, 8}};
-constexpr int kNumVariants = 8;
-constexpr int kRowsVariant = 6;
-// conv_wgrad_rect only: the row-image kernel with segments chosen for the fewest staged rows, an
-// LDS ring sized to the segment, dw-layout partials: 8 / 9 / 10 = 32-channel tiles with a 2 / 3 /
-// 4-stage ring, 11 / 12 = 64-channel tiles with a 3 / 4-stage ring
-constexpr int kRowsExFirst = 8, kRowsExLast = 12;
-struct RowsEx {
-    int ct, stages;
-};
-constexpr RowsEx kRowsEx[] = {{32, 2}, {32, 3}, {32, 4}, {64, 3}, {64, 4}};
-
-bool rows_supported(int Cin, int Cout, int ks, int stride) {
-    return ks == 3 && stride == 1 && Cin % 64 == 0 && Cout % 64 == 0;
-}
-// KUNGFU_WGRAD_PLAN (dev knob): 2 (default) = the round-6 plan rules below, 1 = the round-5 ones
-int wgrad_plan_rules() {
-    static const int v = dev_knob("KUNGFU_WGRAD_PLAN", 2);
-    return v;
+template <int WM, int WN, int TN = 4>
+void reduce_tiles(const float *part, void *dw, const WGeo &g, bool out_f32, bool accumulate, hipStream_t s) {
+    const WgradReduceLaunch r = wgrad_reduce_launch(static_cast<int64_t>(g.tiles) * (64 * WM) * (16 * TN * WN) / 4, g.splits);
+    wgrad_reduce_kernel<WM, WN, TN><<<r.grid, 256, 0, s>>>(part, dw, g, out_f32, accumulate, r.sg_log2);
 }
 
-// default for the narrow channel counts (tools/bench_wgrad.py), and (round 6) for every stride-1 3x3:
-// ResNet-50's 14 x 14 256->256 and 7 x 7 512->512 measured 113 -> 93 us on it (r6t36), VGG-16's
-// 56 x 56 128->256 / 256->256 673 -> 766 / 688 -> 788 TF/s (r6t43, profiles/r6_wgrad_plan.md)
-bool rows_default(int Cin, int Cout, int ks, int stride, int64_t /*P*/) {
-    if (!rows_supported(Cin, Cout, ks, stride)) return false;
-    return (Cin <= 128 && Cout <= 128) || wgrad_plan_rules() >= 2;
-}
-
-RGeo rows_segments(int N, int H, int W, int Cin, int Cout) {
-    RGeo g{};
-    g.N = N, g.H = H, g.W = W, g.C = Cin, g.K = Cout;
-    if (W >= 64) {
-        g.L = 64, g.R = 1, g.spr = (W + 63) / 64, g.gpi = H;
-    } else {
-        g.L = W, g.R = 64 / W, g.spr = 1, g.gpi = (H + g.R - 1) / g.R;
-    }
-    g.nseg = N * g.gpi * g.spr;
-    g.XW = g.L + 2;
-    g.xrows = (g.R + 2) * g.XW;
-    g.xpieces = (g.xrows + 7) / 8;
-    g.mtiles = Cout / 64, g.ntiles = Cin / 64;
-    g.tiles = g.mtiles * g.ntiles * 9;
-    return g;
-}
-
-RGeo make_rgeo(int N, int H, int W, int Cin, int Cout, const WgradPlan &plan) {
-    RGeo g = rows_segments(N, H, W, Cin, Cout);
-    if (g.xpieces > 25) throw std::invalid_argument("conv_wgrad rows: input image exceeds the stage");
-    g.splits = plan.splits;
-    g.kps = plan.kps;
-    return g;
-}
-
-uint64_t magic40(int d) { return (uint64_t(1) << 40) / static_cast<uint64_t>(d) + 1; }
-
-WGeo make_geo(int N, int H, int W, int Cin, int Cout, int ks, int stride, const WgradPlan &plan) {
-    // (tap-tiled variants 0-5 only)
-    WGeo g;
-    const int pad = (ks - 1) / 2;
-    g.N = N, g.H = H, g.W = W, g.C = Cin, g.K = Cout;
-    g.OH = (H + 2 * pad - ks) / stride + 1;
-    g.OW = (W + 2 * pad - ks) / stride + 1;
-    g.HW = g.OH * g.OW;
-    g.P = N * g.HW;
-    g.m_hw = magic40(g.HW);
-    g.m_ow = magic40(g.OW);
-    const Tile t = kTiles[plan.variant];
-    g.mtiles = Cout / t.bm();
-    g.ntiles = Cin / t.bn();
-    g.taps = ks * ks;
-    g.kwin = ks, g.ph = g.pw = pad;
-    g.tiles = g.mtiles * g.ntiles * g.taps;
-    g.splits = plan.splits;
-    g.kps = plan.kps;
+// the fields wgrad_reduce_kernel reads, for the row-image kernels' 64 x 64 partial tiles
+WGeo reduce_geo(int Cin, int Cout, int mtiles, int ntiles, int taps, int tiles, int splits) {
+    WGeo g{};
+    g.C = Cin, g.K = Cout, g.mtiles = mtiles, g.ntiles = ntiles, g.taps = taps, g.tiles = tiles, g.splits = splits;
     return g;
 }
 
@@ -1009,391 +913,32 @@ void launch_t(const uint16_t *dy, const uint16_t *x, void *dw, float *part, cons
     // (256x256 tiles with four 32-pixel stages, KB = 32, instead of two 64-pixel ones: measured no better, r4t1)
     wgrad_kernel<KS, S, WM, WN, STAGES, TN><<<g.tiles * g.splits, 64 * WM * WN, 0, s>>>(
         dy, x, part, dw, reinterpret_cast<const uint16_t *>(zero_page()), g, out_f32, accumulate, atomic_out, stagger);
-    if (g.splits > 1 && !atomic_out) {
-        const int64_t total = static_cast<int64_t>(g.tiles) * (64 * WM) * (16 * TN * WN) / 4;
-        int sgl = 0;  // split groups: enough blocks for the chip, at most 64 groups, <= splits
-        while (sgl < 6 && (2 << sgl) <= g.splits && (total << (sgl + 1)) <= int64_t(256) * 2048) ++sgl;
-        const int64_t grid = (total + (256 >> sgl) - 1) / (256 >> sgl);
-        wgrad_reduce_kernel<WM, WN, TN><<<static_cast<int>(grid), 256, 0, s>>>(part, dw, g, out_f32, accumulate, sgl);
-    }
+    if (g.splits > 1 && !atomic_out) reduce_tiles<WM, WN, TN>(part, dw, g, out_f32, accumulate, s);
 }
 
 template <int KS, int S>
 void launch_ks(const uint16_t *dy, const uint16_t *x, void *dw, float *part, const WGeo &g, int variant,
                bool out_f32, bool accumulate, bool atomic_out, hipStream_t s) {
     switch (variant) {
-    case 0: launch_t<KS, S, 2, 2>(dy, x, dw, part, g, out_f32, accumulate, atomic_out, s); break;
-    case 1: launch_t<KS, S, 2, 1>(dy, x, dw, part, g, out_f32, accumulate, atomic_out, s); break;
-    case 2: launch_t<KS, S, 1, 2>(dy, x, dw, part, g, out_f32, accumulate, atomic_out, s); break;
-    case 3: launch_t<KS, S, 1, 1>(dy, x, dw, part, g, out_f32, accumulate, atomic_out, s); break;
-    case 4: launch_t<KS, S, 4, 2>(dy, x, dw, part, g, out_f32, accumulate, atomic_out, s); break;
-    case 5: launch_t<KS, S, 2, 4>(dy, x, dw, part, g, out_f32, accumulate, atomic_out, s); break;
-    default: launch_t<KS, S, 4, 2, 8>(dy, x, dw, part, g, out_f32, accumulate, atomic_out, s); break;
+    case kWgradTile128x128: launch_t<KS, S, 2, 2>(dy, x, dw, part, g, out_f32, accumulate, atomic_out, s); break;
+    case kWgradTile128x64: launch_t<KS, S, 2, 1>(dy, x, dw, part, g, out_f32, accumulate, atomic_out, s); break;
+    case kWgradTile64x128: launch_t<KS, S, 1, 2>(dy, x, dw, part, g, out_f32, accumulate, atomic_out, s); break;
+    case kWgradTile64x64: launch_t<KS, S, 1, 1>(dy, x, dw, part, g, out_f32, accumulate, atomic_out, s); break;
+    case kWgradTile256x128: launch_t<KS, S, 4, 2>(dy, x, dw, part, g, out_f32, accumulate, atomic_out, s); break;
+    case kWgradTile128x256: launch_t<KS, S, 2, 4>(dy, x, dw, part, g, out_f32, accumulate, atomic_out, s); break;
+    default: launch_t<KS, S, 4, 2, 8>(dy, x, dw, part, g, out_f32, accumulate, atomic_out, s); break;  // 256x256
     }
 }
 
-}  // namespace
-
-int conv_wgrad_variants() { return kNumVariants; }
-
-int64_t conv_wgrad_max_pixels(int N, int H, int W, int Cin, int Cout, int ks, int stride) {
-    // the tap-tiled kernel's 40-bit magic division holds < 2^23 output pixels; the row-image
-    // kernel only needs 32-bit element offsets (checked by the caller)
-    const WgradPlan pl = conv_wgrad_plan(N, H, W, Cin, Cout, ks, stride, -1, -1);
-    return pl.variant == kRowsVariant ? (int64_t(1) << 31) : (int64_t(1) << 23);
-}
-
-bool conv_wgrad_supported(int Cin, int Cout, int ks, int stride) {
-    return (ks == 1 || ks == 3) && (stride == 1 || stride == 2) && Cin % 64 == 0 && Cout % 64 == 0 && Cin >= 64 &&
-           Cout >= 64;
-}
-
-WgradPlan conv_wgrad_plan(int N, int H, int W, int Cin, int Cout, int ks, int stride, int variant, int splits) {
-    WgradPlan pl;
-    const int64_t work = static_cast<int64_t>(Cin) * Cout * ks * ks;
-    if (variant < 0 && rows_default(Cin, Cout, ks, stride, static_cast<int64_t>(N) * H * W)) variant = kRowsVariant;
-    if (variant == kRowsVariant) {
-        if (!rows_supported(Cin, Cout, ks, stride)) throw std::invalid_argument("conv_wgrad: rows variant needs 3x3/s1");
-        pl.variant = variant;
-        const RGeo rg = rows_segments(N, H, W, Cin, Cout);
-        const int ct = rg.mtiles * rg.ntiles;
-        // one workgroup of 9 waves per CU (round 6; two per CU through round 5): half the split
-        // partials to reduce -- 56 x 56 64->64 119 -> 89 us, 28 x 28 128->128 108 -> 84 (r6t36)
-        const int per = wgrad_plan_rules() >= 2 ? 256 : 512;
-        if (splits < 0) splits = std::max(1, (per + ct / 2) / ct);
-        splits = std::max(1, std::min(splits, std::max(1, rg.nseg / 4)));
-        pl.kps = (rg.nseg + splits - 1) / splits;
-        pl.splits = (rg.nseg + pl.kps - 1) / pl.kps;
-        pl.ws_floats = pl.splits > 1 ? static_cast<int64_t>(pl.splits) * ct * 9 * 4096 : 0;
-        return pl;
-    }
-    if (variant < 0) {
-        // tools/bench_wgrad.py --sweep (profiles/README.md): 8-wave 256x128 tiles once the
-        // GEMM is big enough, else the largest 4/2/1-wave tile the channel counts allow
-        // tools/bench_wgrad_1x1.py: 256x256 for the large long-K linear-layer products (BERT-base
-        // 768x3072 at 16 K tokens: 133 -> 87 us); ResNet's 1x1 shapes keep 256x128 (their split-K
-        // partials of 256x256 tiles cost more than the extra MFMA density saves)
-        const int64_t P1 = static_cast<int64_t>(N) * ((H + 2 * ((ks - 1) / 2) - ks) / stride + 1) *
-                           ((W + 2 * ((ks - 1) / 2) - ks) / stride + 1);
-        // (round 6: and the wide 1x1 products on >= 200,704 output pixels -- 28 x 28 512->256 103 -> 77 us,
-        // 56 x 56 256->512 / s2 103 -> 90; ResNet-50 20.09-20.13 -> 20.07 ms/step, r6t36 / r6t37)
-        if (Cout % 256 == 0 && Cin % 256 == 0 && ks == 1 && (work >= 1500000 || (wgrad_plan_rules() >= 2 && P1 >= 200704)))
-            variant = 7;
-        else if (Cout % 256 == 0 && Cin % 128 == 0) variant = 4;
-        else if (Cout % 128 == 0 && Cin % 256 == 0 && work >= (wgrad_plan_rules() >= 2 ? 32768 : 131072)) variant = 5;
-        // (round 6: 128x256 from 32 K outputs -- 56 x 56 256->128 158 -> 111 us, 28 x 28 512->128 73 -> 60, r6t36)
-        else if (Cout % 128 == 0 && Cin % 128 == 0) variant = 0;
-        else if (Cout % 128 == 0) variant = 1;
-        else if (Cin % 128 == 0) variant = 2;
-        else variant = 3;
-    }
-    const Tile t = kTiles[variant];
-    if (t.wm == 0 || Cout % t.bm() != 0 || Cin % t.bn() != 0) throw std::invalid_argument("conv_wgrad: tile/channel mismatch");
-    pl.variant = variant;
-    const int pad = (ks - 1) / 2;
-    const int OH = (H + 2 * pad - ks) / stride + 1, OW = (W + 2 * pad - ks) / stride + 1;
-    const int64_t P = static_cast<int64_t>(N) * OH * OW;
-    const int ksteps = static_cast<int>((P + kBK - 1) / kBK);
-    const int tiles = (Cout / t.bm()) * (Cin / t.bn()) * ks * ks;
-    if (splits < 0) {
-        // workgroups per launch: one per CU for the 4/8-wave tiles (2 for 3x3), more for the
-        // 1-2 wave tiles, so every CU keeps >= ~48 KB of loads in flight; >= 4 K-steps per split
-        const int nw = t.wm * t.wn;
-        int target = 256 * (nw >= 4 ? 1 : 2);
-        if (ks == 3) target *= nw == 1 ? 4 : 2;
-        splits = (target + tiles / 2) / tiles;
-        // large-pixel 3x3 shapes (VGG-16's 56..224 layers, batch 256): ~100 K-steps per split
-        // and up to 512 splits (tools/bench_vgg_wgrad.py: 112x112 128->128 313 -> 477 TF/s,
-        // 56x56 128->256 587 -> 761 TF/s; 28x28 and smaller keep the default)
-        if (ks == 3 && P >= 800000) splits = std::max(splits, std::min(512, ksteps / 96));
-        splits = std::max(1, std::min(splits, ksteps / 4));
-    }
-    splits = std::max(1, std::min(splits, ksteps));
-    pl.kps = (ksteps + splits - 1) / splits;
-    pl.splits = (ksteps + pl.kps - 1) / pl.kps;  // no empty split
-    pl.ws_floats = pl.splits > 1 ? static_cast<int64_t>(pl.splits) * tiles * t.bm() * t.bn() : 0;
-    return pl;
-}
-
-void launch_conv_wgrad(const uint16_t *dy, const uint16_t *x, void *dw, float *part, int N, int H, int W, int Cin,
-                       int Cout, int ks, int stride, const WgradPlan &plan, bool out_f32, bool accumulate,
-                       hipStream_t s, bool atomics) {
-    // split-K accumulating into an f32 destination: every split adds its tile with atomics (unless
-    // `atomics` is off: then partial tiles + the deterministic reduce, which adds into dw)
-    const bool atomic_out = atomics && out_f32 && accumulate && plan.splits > 1;
-    if (!conv_wgrad_supported(Cin, Cout, ks, stride)) throw std::invalid_argument("conv_wgrad: unsupported shape");
-    if (plan.variant == kRowsVariant) {
-        if (!rows_supported(Cin, Cout, ks, stride)) throw std::invalid_argument("conv_wgrad: rows variant needs 3x3/s1");
-        const RGeo rg = make_rgeo(N, H, W, Cin, Cout, plan);
-        wgrad_rows_kernel<2><<<rg.mtiles * rg.ntiles * rg.splits, 576, 0, s>>>(
-            dy, x, part, dw, reinterpret_cast<const uint16_t *>(zero_page()), rg, out_f32, accumulate, atomic_out,
-            rows_stagger(false));
-        if (rg.splits > 1 && !atomic_out) {
-            WGeo g{};
-            g.C = Cin, g.K = Cout, g.mtiles = rg.mtiles, g.ntiles = rg.ntiles, g.taps = 9, g.tiles = rg.tiles;
-            g.splits = rg.splits;
-            const int64_t tot = static_cast<int64_t>(g.tiles) * 1024;
-            int sgl = 0;
-            while (sgl < 6 && (2 << sgl) <= g.splits && (tot << (sgl + 1)) <= int64_t(256) * 2048) ++sgl;
-            const int64_t grid = (tot + (256 >> sgl) - 1) / (256 >> sgl);
-            wgrad_reduce_kernel<1, 1><<<static_cast<int>(grid), 256, 0, s>>>(part, dw, g, out_f32, accumulate, sgl);
-        }
-        return;
-    }
-    const WGeo g = make_geo(N, H, W, Cin, Cout, ks, stride, plan);
-    if (static_cast<int64_t>(g.P) * g.HW >= (int64_t(1) << 40) || g.P >= (1 << 23))
+void launch_tiled(const uint16_t *dy, const uint16_t *x, void *dw, float *part, const WgradPlan &plan, bool out_f32,
+                  bool accumulate, bool atomic_out, hipStream_t s) {
+    const WGeo &g = plan.tiled;
+    const int64_t P = plan.shape.P();
+    if (P * g.HW >= (int64_t(1) << 40) || P >= (1 << 23))
         throw std::invalid_argument("conv_wgrad: too many pixels for the 40-bit division");
-    if (g.splits > 1 && !atomic_out && part == nullptr) throw std::invalid_argument("conv_wgrad: split-K needs the workspace");
-    if (ks == 1) {
-        if (stride == 1) launch_ks<1, 1>(dy, x, dw, part, g, plan.variant, out_f32, accumulate, atomic_out, s);
-        else launch_ks<1, 2>(dy, x, dw, part, g, plan.variant, out_f32, accumulate, atomic_out, s);
-    } else {
-        if (stride == 1) launch_ks<3, 1>(dy, x, dw, part, g, plan.variant, out_f32, accumulate, atomic_out, s);
-        else launch_ks<3, 2>(dy, x, dw, part, g, plan.variant, out_f32, accumulate, atomic_out, s);
-    }
-}
-
-// ---- any KH x KW window, padding, channel counts % 8 (Inception-v3) -----------------------
-
-bool conv_wgrad_rect_supported(int Cin, int Cout, int kh, int kw, int stride) {
-    return Cin % 8 == 0 && Cout % 8 == 0 && Cin >= 16 && Cout >= 16 && (stride == 1 || stride == 2) && kh >= 1 &&
-           kw >= 1 && kh * kw <= 49;
-}
-
-namespace {
-// tile: 128 rows where the channel count reaches it (less zero padding otherwise)
-int rect_variant(int Cin, int Cout) { return Cout >= 128 ? (Cin >= 128 ? 0 : 1) : (Cin >= 128 ? 2 : 3); }
-
-WGeo make_rect_geo(int N, int H, int W, int Cin, int Cout, int kh, int kw, int ph, int pw, int stride, int variant) {
-    WGeo g{};
-    g.N = N, g.H = H, g.W = W, g.C = Cin, g.K = Cout;
-    g.OH = (H + 2 * ph - kh) / stride + 1;
-    g.OW = (W + 2 * pw - kw) / stride + 1;
-    g.HW = g.OH * g.OW;
-    g.P = N * g.HW;
-    g.m_hw = magic40(g.HW);
-    g.m_ow = magic40(g.OW);
-    const Tile t = kTiles[variant];
-    g.mtiles = (Cout + t.bm() - 1) / t.bm();
-    g.ntiles = (Cin + t.bn() - 1) / t.bn();
-    g.taps = kh * kw;
-    g.tiles = g.mtiles * g.ntiles * g.taps;
-    g.kwin = kw, g.ph = ph, g.pw = pw;
-    return g;
-}
-}  // namespace
-
-namespace {
-// the row-image kernel's segments / tap groups for a stride-1 KH x KW window (xpieces > 25: unsupported)
-RRGeo rows_rect_geo(int N, int H, int W, int Cin, int Cout, int kh, int kw, int ph, int pw, int ct = 64,
-                    bool legacy = true, int stride = 1) {
-    RRGeo g{};
-    g.N = N, g.H = H, g.W = W, g.C = Cin, g.K = Cout, g.S = stride;
-    g.OH = (H + 2 * ph - kh) / stride + 1, g.OW = (W + 2 * pw - kw) / stride + 1;
-    g.KH = kh, g.KW = kw, g.ph = ph, g.pw = pw, g.taps = kh * kw;
-    const int nwv = g.taps % 7 == 0 ? 7 : 9;
-    g.tgroups = (g.taps + nwv - 1) / nwv;
-    auto shape = [&](int L, int R) {
-        g.L = L, g.R = R, g.spr = (g.OW + L - 1) / L, g.gpi = (g.OH + R - 1) / R;
-        g.nseg = N * g.gpi * g.spr;
-        g.XW = stride * (g.L - 1) + kw;
-        g.xrows = (stride * (g.R - 1) + kh) * g.XW;
-    };
-    if (legacy) {
-        if (g.OW >= 64) shape(64, 1);
-        else shape(g.OW, 64 / g.OW);
-    } else {
-        // 64-byte rows: the R x L segment of 64 slots with the fewest staged rows (dy + image) in
-        // total -- R > 1 on the wide maps too (Conv2d_2a's 109-wide rows: 16 x 4 stages 1.7 input
-        // rows per output pixel where 64 x 1 stages 3.1)
-        int64_t best = -1;
-        int bl = 64, br = 1;
-        for (int R = 1; R <= 64; ++R) {
-            const int L = std::min(g.OW, 64 / R);
-            if (L < 1 || (R > 1 && (R - 1) * L >= 64)) break;
-            if (R > g.OH + 1) break;
-            shape(L, R);
-            if (g.xrows * 2 * ct > 25 * 1024) continue;
-            const int64_t cost = static_cast<int64_t>(g.nseg) * (64 + g.xrows);
-            if (best < 0 || cost < best) best = cost, bl = L, br = R;
-        }
-        shape(bl, br);
-    }
-    g.xpieces = (g.xrows * 2 * ct + 1023) / 1024;
-    g.mtiles = (Cout + ct - 1) / ct, g.ntiles = (Cin + ct - 1) / ct;
-    g.stage = 64 * 2 * ct + (legacy ? 26 : g.xpieces + 1) * 1024;
-    g.tiles = g.mtiles * g.ntiles * g.taps;
-    return g;
-}
-}  // namespace
-
-bool conv_wgrad_rows_rect_supported(int N, int H, int W, int Cin, int Cout, int kh, int kw, int ph, int pw,
-                                    int stride) {
-    if ((stride != 1 && stride != 2) || kh * kw < 2 || !conv_wgrad_rect_supported(Cin, Cout, kh, kw, stride)) return false;
-    if (H + 2 * ph - kh < 0 || W + 2 * pw - kw < 0) return false;
-    if (stride == 1) return rows_rect_geo(N, H, W, Cin, Cout, kh, kw, ph, pw).xpieces <= 25;
-    // stride 2: the kRowsEx variants only (64-channel tiles bound the staged image)
-    return rows_rect_geo(N, H, W, Cin, Cout, kh, kw, ph, pw, 64, false, 2).xpieces <= 25;
-}
-
-// Row-image variant per shape, from the Inception-v3 sweep (profiles/r5_inception_wgrad.md): 32-channel
-// tiles (8) when both channel counts fit one; the 64-tile kernel as before (6) when both are
-// multiples of 64; otherwise 64-channel tiles on the fewest-rows segments with a 4-stage ring (12) on
-// the small maps (<= 32 x 32: few segments per workgroup, the ring's depth pays) when it fits in
-// 96 KB, else a 3-stage ring (11: two workgroups per CU on the 54 x 54 / 109 x 109 maps)
-int conv_wgrad_rows_rect_auto(int N, int H, int W, int Cin, int Cout, int kh, int kw, int ph, int pw, int stride) {
-    if (Cin <= 32 && Cout <= 32) return 8;
-    if (stride == 2) {
-        // r5 stride-2 sweep: 25x25 96->96 34 us on 10 (MIOpen 50), 288->384 241 on 8 (tap-tiled 266,
-        // MIOpen 324), 12x12 192->192 / 192->320 33 / 41 on 12 (MIOpen 29 / 41)
-        if (Cin % 64 != 0 || Cout % 64 != 0) return (H * W <= 1024 && Cout <= 128) ? 10 : 8;
-        return 12;
-    }
-    if (stride == 1 && Cin % 64 == 0 && Cout % 64 == 0) return kRowsVariant;
-    const RRGeo rg = rows_rect_geo(N, H, W, Cin, Cout, kh, kw, ph, pw, 64, false, stride);
-    return (H * W <= 1024 && 4 * rg.stage <= 96 * 1024) ? 12 : 11;
-}
-
-WgradPlan conv_wgrad_rect_plan(int N, int H, int W, int Cin, int Cout, int kh, int kw, int ph, int pw, int stride,
-                               int variant) {
-    WgradPlan pl;
-    if (variant == 13) {
-        if (!conv_wgrad_rows_rect_supported(N, H, W, Cin, Cout, kh, kw, ph, pw, stride))
-            throw std::invalid_argument("conv_wgrad_rect: row-image variant unsupported for this shape");
-        variant = conv_wgrad_rows_rect_auto(N, H, W, Cin, Cout, kh, kw, ph, pw, stride);
-    }
-    if (variant >= kRowsExFirst && variant <= kRowsExLast) {
-        if (!conv_wgrad_rows_rect_supported(N, H, W, Cin, Cout, kh, kw, ph, pw, stride))
-            throw std::invalid_argument("conv_wgrad_rect: row-image variant unsupported for this shape");
-        const RowsEx vx = kRowsEx[variant - kRowsExFirst];
-        const RRGeo rg = rows_rect_geo(N, H, W, Cin, Cout, kh, kw, ph, pw, vx.ct, false, stride);
-        if (rg.xpieces > 25) throw std::invalid_argument("conv_wgrad_rect: image segment too large for this variant");
-        pl.variant = variant;
-        const int ct = rg.mtiles * rg.ntiles * rg.tgroups;
-        // as many workgroups as fit at once: LDS ring per CU, <= 3 of 7-9 waves
-        const int occ = std::max(1, std::min(3, 160 * 1024 / (vx.stages * rg.stage)));
-        int splits = std::max(1, (256 * occ + ct / 2) / ct);
-        splits = std::max(1, std::min(splits, std::max(1, rg.nseg / 4)));
-        pl.kps = (rg.nseg + splits - 1) / splits;
-        pl.splits = (rg.nseg + pl.kps - 1) / pl.kps;
-        pl.ws_floats = pl.splits > 1 ? static_cast<int64_t>(pl.splits) * Cout * rg.taps * Cin : 0;
-        return pl;
-    }
-    if (variant == kRowsVariant) {
-        if (stride != 1 || !conv_wgrad_rows_rect_supported(N, H, W, Cin, Cout, kh, kw, ph, pw, stride))
-            throw std::invalid_argument("conv_wgrad_rect: row-image variant unsupported for this shape");
-        const RRGeo rg = rows_rect_geo(N, H, W, Cin, Cout, kh, kw, ph, pw);
-        pl.variant = variant;
-        const int ct = rg.mtiles * rg.ntiles * rg.tgroups;
-        // ~2 workgroups of 7-9 waves per CU, >= 4 segments per split
-        int splits = std::max(1, (512 + ct / 2) / ct);
-        splits = std::max(1, std::min(splits, std::max(1, rg.nseg / 4)));
-        pl.kps = (rg.nseg + splits - 1) / splits;
-        pl.splits = (rg.nseg + pl.kps - 1) / pl.kps;
-        pl.ws_floats = pl.splits > 1 ? static_cast<int64_t>(pl.splits) * rg.tiles * 4096 : 0;
-        return pl;
-    }
-    pl.variant = rect_variant(Cin, Cout);
-    WGeo g = make_rect_geo(N, H, W, Cin, Cout, kh, kw, ph, pw, stride, pl.variant);
-    const Tile t = kTiles[pl.variant];
-    const int ksteps = (g.P + kBK - 1) / kBK;
-    const int nw = t.wm * t.wn;
-    int target = 256 * (nw >= 4 ? 1 : 2) * (g.taps > 1 ? 2 : 1);
-    int splits = (target + g.tiles / 2) / g.tiles;
-    splits = std::max(1, std::min(splits, ksteps / 4));
-    splits = std::max(1, std::min(splits, ksteps));
-    pl.kps = (ksteps + splits - 1) / splits;
-    pl.splits = (ksteps + pl.kps - 1) / pl.kps;
-    pl.ws_floats = pl.splits > 1 ? static_cast<int64_t>(pl.splits) * g.tiles * t.bm() * t.bn() : 0;
-    return pl;
-}
-
-void launch_conv_wgrad_rect(const uint16_t *dy, const uint16_t *x, void *dw, float *part, int N, int H, int W,
-                            int Cin, int Cout, int kh, int kw, int ph, int pw, int stride, const WgradPlan &plan,
-                            bool out_f32, bool accumulate, hipStream_t s) {
-    if (!conv_wgrad_rect_supported(Cin, Cout, kh, kw, stride)) throw std::invalid_argument("conv_wgrad_rect: unsupported");
-    const bool atomic_out = out_f32 && accumulate && plan.splits > 1;
-    if (plan.variant >= kRowsExFirst && plan.variant <= kRowsExLast) {
-        if (!conv_wgrad_rows_rect_supported(N, H, W, Cin, Cout, kh, kw, ph, pw, stride))
-            throw std::invalid_argument("conv_wgrad_rect: row-image variant unsupported for this shape");
-        const RowsEx vx = kRowsEx[plan.variant - kRowsExFirst];
-        RRGeo rg = rows_rect_geo(N, H, W, Cin, Cout, kh, kw, ph, pw, vx.ct, false, stride);
-        rg.splits = plan.splits, rg.kps = plan.kps;
-        if (rg.splits > 1 && !atomic_out && part == nullptr) throw std::invalid_argument("conv_wgrad_rect: needs the workspace");
-        const int grid = rg.mtiles * rg.ntiles * rg.tgroups * rg.splits;
-        const uint16_t *z = reinterpret_cast<const uint16_t *>(zero_page());
-        const int lds = vx.stages * rg.stage;
-        const bool t7 = rg.taps % 7 == 0;
-        static bool attr_set[kRowsExLast - kRowsExFirst + 1][2] = {};  // per instantiation, once
-        auto go = [&](auto kern, int nwv) {
-            bool &done = attr_set[plan.variant - kRowsExFirst][t7 ? 1 : 0];
-            if (!done) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          160 * 1024);
-                done = true;
-            }
-            kern<<<grid, 64 * nwv, lds, s>>>(dy, x, part, dw, z, rg, out_f32, accumulate, atomic_out, rows_stagger(true));
-        };
-        switch (plan.variant) {
-            case 8: t7 ? go(wgrad_rows_rect_kernel<7, 2, 32, true>, 7) : go(wgrad_rows_rect_kernel<9, 2, 32, true>, 9); break;
-            case 9: t7 ? go(wgrad_rows_rect_kernel<7, 3, 32, true>, 7) : go(wgrad_rows_rect_kernel<9, 3, 32, true>, 9); break;
-            case 10: t7 ? go(wgrad_rows_rect_kernel<7, 4, 32, true>, 7) : go(wgrad_rows_rect_kernel<9, 4, 32, true>, 9); break;
-            case 11: t7 ? go(wgrad_rows_rect_kernel<7, 3, 64, true>, 7) : go(wgrad_rows_rect_kernel<9, 3, 64, true>, 9); break;
-            default: t7 ? go(wgrad_rows_rect_kernel<7, 4, 64, true>, 7) : go(wgrad_rows_rect_kernel<9, 4, 64, true>, 9); break;
-        }
-        if (rg.splits > 1 && !atomic_out) {
-            const int64_t n = static_cast<int64_t>(Cout) * rg.taps * Cin;
-            // split groups: up to 64, ~8 splits each, while >= 1,024 blocks of columns... or fewer
-            int sgl = 0;
-            while (sgl < 6 && (8 << sgl) < rg.splits && (n / 4) * (2 << sgl) <= int64_t(1024) * 256) ++sgl;
-            const int cols = 256 >> sgl;
-            wgrad_dense_reduce_kernel<<<static_cast<int>((n / 4 + cols - 1) / cols), 256, 0, s>>>(
-                part, rg.splits, n, dw, out_f32, accumulate, sgl);
-        }
-        return;
-    }
-    if (plan.variant == kRowsVariant) {
-        if (stride != 1 || !conv_wgrad_rows_rect_supported(N, H, W, Cin, Cout, kh, kw, ph, pw, stride))
-            throw std::invalid_argument("conv_wgrad_rect: row-image variant unsupported for this shape");
-        RRGeo rg = rows_rect_geo(N, H, W, Cin, Cout, kh, kw, ph, pw);
-        rg.splits = plan.splits, rg.kps = plan.kps;
-        if (rg.splits > 1 && !atomic_out && part == nullptr) throw std::invalid_argument("conv_wgrad_rect: needs the workspace");
-        const int grid = rg.mtiles * rg.ntiles * rg.tgroups * rg.splits;
-        const uint16_t *z = reinterpret_cast<const uint16_t *>(zero_page());
-        static const bool attr = [] {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(wgrad_rows_rect_kernel<7, 2>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(wgrad_rows_rect_kernel<9, 2>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            return true;
-        }();
-        (void)attr;
-        if (rg.taps % 7 == 0)
-            wgrad_rows_rect_kernel<7, 2><<<grid, 64 * 7, 2 * rg.stage, s>>>(dy, x, part, dw, z, rg, out_f32, accumulate,
-                                                                          atomic_out, rows_stagger(true));
-        else
-            wgrad_rows_rect_kernel<9, 2><<<grid, 64 * 9, 2 * rg.stage, s>>>(dy, x, part, dw, z, rg, out_f32, accumulate,
-                                                                          atomic_out, rows_stagger(true));
-        if (rg.splits > 1 && !atomic_out) {
-            WGeo g{};
-            g.C = Cin, g.K = Cout, g.mtiles = rg.mtiles, g.ntiles = rg.ntiles, g.taps = rg.taps, g.tiles = rg.tiles;
-            g.splits = rg.splits;
-            const int64_t tot = static_cast<int64_t>(g.tiles) * 1024;
-            int sgl = 0;
-            while (sgl < 6 && (2 << sgl) <= g.splits && (tot << (sgl + 1)) <= int64_t(256) * 2048) ++sgl;
-            const int64_t rgrid = (tot + (256 >> sgl) - 1) / (256 >> sgl);
-            wgrad_reduce_kernel<1, 1><<<static_cast<int>(rgrid), 256, 0, s>>>(part, dw, g, out_f32, accumulate, sgl);
-        }
-        return;
-    }
-    WGeo g = make_rect_geo(N, H, W, Cin, Cout, kh, kw, ph, pw, stride, plan.variant);
-    g.splits = plan.splits;
-    g.kps = plan.kps;
-    if (static_cast<int64_t>(g.P) * g.HW >= (int64_t(1) << 40) || g.P >= (1 << 23))
-        throw std::invalid_argument("conv_wgrad_rect: too many pixels for the 40-bit division");
-    if (g.splits > 1 && !atomic_out && part == nullptr) throw std::invalid_argument("conv_wgrad_rect: needs the workspace");
-    const bool k1 = kh == 1 && kw == 1 && ph == 0 && pw == 0, k3 = kh == 3 && kw == 3 && ph == 1 && pw == 1;
-    if (stride == 1) {
+    // 1x1 and 3x3 / pad 1 have the window compiled in, any other window reads it from g
+    const bool k1 = g.taps == 1 && g.ph == 0 && g.pw == 0, k3 = g.taps == 9 && g.kwin == 3 && g.ph == 1 && g.pw == 1;
+    if (plan.shape.stride == 1) {
         if (k1) launch_ks<1, 1>(dy, x, dw, part, g, plan.variant, out_f32, accumulate, atomic_out, s);
         else if (k3) launch_ks<3, 1>(dy, x, dw, part, g, plan.variant, out_f32, accumulate, atomic_out, s);
         else launch_ks<0, 1>(dy, x, dw, part, g, plan.variant, out_f32, accumulate, atomic_out, s);
@@ -1401,6 +946,68 @@ void launch_conv_wgrad_rect(const uint16_t *dy, const uint16_t *x, void *dw, flo
         if (k1) launch_ks<1, 2>(dy, x, dw, part, g, plan.variant, out_f32, accumulate, atomic_out, s);
         else if (k3) launch_ks<3, 2>(dy, x, dw, part, g, plan.variant, out_f32, accumulate, atomic_out, s);
         else launch_ks<0, 2>(dy, x, dw, part, g, plan.variant, out_f32, accumulate, atomic_out, s);
+    }
+}
+
+// RowsRect: wgrad_rows_rect_kernel<7|9, 2>, 64 x 64 partial tiles; RowsRing: <7|9, stages, ct, true>, dw-layout partials
+void launch_rows_rect(const uint16_t *dy, const uint16_t *x, void *dw, float *part, const WgradPlan &plan, bool out_f32,
+                      bool accumulate, bool atomic_out, hipStream_t s) {
+    const RRGeo &g = plan.rect;
+    const int grid = g.mtiles * g.ntiles * g.tgroups * g.splits;
+    const uint16_t *z = reinterpret_cast<const uint16_t *>(zero_page());
+    const int lds = plan.stages * g.stage;
+    const bool t7 = g.taps % 7 == 0;  // 7 waves for the 1x7 / 7x1 / 7x7 windows, else 9
+    static bool attr_set[kWgradRing64x4 + 1][2] = {};  // per instantiation, once
+    auto go = [&](auto kern, int nwv) {
+        bool &done = attr_set[plan.variant][t7 ? 1 : 0];
+        if (!done) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      160 * 1024);
+            done = true;
+        }
+        kern<<<grid, 64 * nwv, lds, s>>>(dy, x, part, dw, z, g, out_f32, accumulate, atomic_out, 1);
+    };
+    switch (plan.variant) {
+    case kWgradRows: t7 ? go(wgrad_rows_rect_kernel<7, 2>, 7) : go(wgrad_rows_rect_kernel<9, 2>, 9); break;
+    case kWgradRing32x2: t7 ? go(wgrad_rows_rect_kernel<7, 2, 32, true>, 7) : go(wgrad_rows_rect_kernel<9, 2, 32, true>, 9); break;
+    case kWgradRing32x3: t7 ? go(wgrad_rows_rect_kernel<7, 3, 32, true>, 7) : go(wgrad_rows_rect_kernel<9, 3, 32, true>, 9); break;
+    case kWgradRing32x4: t7 ? go(wgrad_rows_rect_kernel<7, 4, 32, true>, 7) : go(wgrad_rows_rect_kernel<9, 4, 32, true>, 9); break;
+    case kWgradRing64x3: t7 ? go(wgrad_rows_rect_kernel<7, 3, 64, true>, 7) : go(wgrad_rows_rect_kernel<9, 3, 64, true>, 9); break;
+    default: t7 ? go(wgrad_rows_rect_kernel<7, 4, 64, true>, 7) : go(wgrad_rows_rect_kernel<9, 4, 64, true>, 9); break;  // 64x4
+    }
+    if (g.splits == 1 || atomic_out) return;
+    if (plan.kernel == WgradKernel::RowsRect) {
+        reduce_tiles<1, 1>(part, dw, reduce_geo(g.C, g.K, g.mtiles, g.ntiles, g.taps, g.tiles, g.splits), out_f32, accumulate, s);
+    } else {
+        const int64_t n = static_cast<int64_t>(g.K) * g.taps * g.C;
+        // split groups: up to 64, ~8 splits each, while >= 1,024 blocks of columns... or fewer
+        int sgl = 0;
+        while (sgl < 6 && (8 << sgl) < g.splits && (n / 4) * (2 << sgl) <= int64_t(1024) * 256) ++sgl;
+        const int cols = 256 >> sgl;
+        wgrad_dense_reduce_kernel<<<static_cast<int>((n / 4 + cols - 1) / cols), 256, 0, s>>>(part, g.splits, n, dw, out_f32,
+                                                                                           accumulate, sgl);
+    }
+}
+
+}  // namespace
+
+void launch_conv_wgrad(const uint16_t *dy, const uint16_t *x, void *dw, float *part, const WgradPlan &plan, bool out_f32,
+                       bool accumulate, hipStream_t s, bool atomics) {
+    // split-K accumulating into an f32 destination: every split adds its tile with atomics (unless
+    // `atomics` is off: then partial tiles + the deterministic reduce, which adds into dw)
+    const bool atomic_out = atomics && out_f32 && accumulate && plan.splits > 1;
+    if (plan.splits > 1 && !atomic_out && part == nullptr) throw std::invalid_argument("conv_wgrad: split-K needs the workspace");
+    switch (plan.kernel) {
+    case WgradKernel::Tiled: launch_tiled(dy, x, dw, part, plan, out_f32, accumulate, atomic_out, s); break;
+    case WgradKernel::Rows3x3: {
+        const RGeo &g = plan.rows;
+        wgrad_rows_kernel<2><<<g.mtiles * g.ntiles * g.splits, 576, 0, s>>>(
+            dy, x, part, dw, reinterpret_cast<const uint16_t *>(zero_page()), g, out_f32, accumulate, atomic_out, 1);
+        if (g.splits > 1 && !atomic_out)
+            reduce_tiles<1, 1>(part, dw, reduce_geo(g.C, g.K, g.mtiles, g.ntiles, 9, g.tiles, g.splits), out_f32, accumulate, s);
+        break;
+    }
+    default: launch_rows_rect(dy, x, dw, part, plan, out_f32, accumulate, atomic_out, s); break;
     }
 }
 

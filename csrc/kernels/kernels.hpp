@@ -5,6 +5,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "wgrad_plan.hpp"
+
 #include <cstddef>
 #include <cstdint>
 #include <string>
@@ -256,40 +258,14 @@ void launch_conv_flip_weight(const uint16_t *w, uint16_t *wt, int Cout, int Cin,
 // Any KH x KW window: the flattened tap index is reversed (taps = KH*KW).
 void launch_conv_flip_weight_taps(const uint16_t *w, uint16_t *wt, int Cout, int Cin, int taps, hipStream_t s);
 
-// Weight gradient of the KS x KS (pad (KS-1)/2, stride 1|2) NHWC convolution as a split-K
-// MFMA GEMM (conv_wgrad.hip): dw[co, kh, kw, ci] = sum_p dy[p, co] * x[pix(p, kh, kw), ci].
-// dw: bf16 (out_f32 = 0) or f32 (out_f32 = 1), [Cout][KS*KS][Cin]; accumulate: dw += result.
-// part: f32 workspace of conv_wgrad_workspace(...) floats (unused when that is 0).
-struct WgradPlan {
-    int variant = 0;  // tile choice
-    int splits = 1;   // K (pixel) splits
-    int kps = 0;      // K-steps per split
-    int64_t ws_floats = 0;
-};
-bool conv_wgrad_supported(int Cin, int Cout, int ks, int stride);
-// output pixels (N*OH*OW) one launch of the default plan handles
-int64_t conv_wgrad_max_pixels(int N, int H, int W, int Cin, int Cout, int ks, int stride);
-WgradPlan conv_wgrad_plan(int N, int H, int W, int Cin, int Cout, int ks, int stride, int variant = -1,
-                          int splits = -1);
-void launch_conv_wgrad(const uint16_t *dy, const uint16_t *x, void *dw, float *part, int N, int H, int W, int Cin,
-                       int Cout, int ks, int stride, const WgradPlan &plan, bool out_f32, bool accumulate,
-                       hipStream_t s, bool atomics = true);
-// Any KH x KW window with zero padding (ph, pw), stride 1|2, Cin / Cout multiples of 8
-// (Inception-v3's windows and channel counts): same kernel, runtime window, zero-padded tiles.
-bool conv_wgrad_rect_supported(int Cin, int Cout, int kh, int kw, int stride);
-// variant 6 (stride 1, multi-tap): the row-image kernel (all taps of a workgroup share one staged
-// input image per 64-pixel segment), else -1 = the tap-tiled split-K kernel.
-WgradPlan conv_wgrad_rect_plan(int N, int H, int W, int Cin, int Cout, int kh, int kw, int ph, int pw, int stride,
-                               int variant = -1);
-// the row-image variant for a stride-1 multi-tap shape (6, or 8 / 11 / 12: see conv_wgrad.hip kRowsEx);
-// conv_wgrad_rect(..., variant = 13) runs it
-int conv_wgrad_rows_rect_auto(int N, int H, int W, int Cin, int Cout, int kh, int kw, int ph, int pw, int stride);
-bool conv_wgrad_rows_rect_supported(int N, int H, int W, int Cin, int Cout, int kh, int kw, int ph, int pw,
-                                    int stride);
-void launch_conv_wgrad_rect(const uint16_t *dy, const uint16_t *x, void *dw, float *part, int N, int H, int W,
-                            int Cin, int Cout, int kh, int kw, int ph, int pw, int stride, const WgradPlan &plan,
-                            bool out_f32, bool accumulate, hipStream_t s);
-int conv_wgrad_variants();
+// Weight gradient of an NHWC bf16 convolution as a split-K MFMA GEMM over the output pixels
+// (conv_wgrad.hip): dw[co, kh, kw, ci] = sum_p dy[p, co] * x[pix(p, kh, kw), ci].  The plan
+// (wgrad_plan.hpp: conv_wgrad_plan) names the kernel, its tile, geometry and splits.
+// dw: bf16 (out_f32 = 0) or f32 (out_f32 = 1), [Cout][KH*KW][Cin]; accumulate: dw += result.
+// part: f32 workspace of plan.ws_floats floats (unused when that is 0).  atomics: split-K into an
+// accumulated f32 dw adds with f32 atomics; off: partial tiles + the deterministic reduce.
+void launch_conv_wgrad(const uint16_t *dy, const uint16_t *x, void *dw, float *part, const WgradPlan &plan,
+                       bool out_f32, bool accumulate, hipStream_t s, bool atomics = true);
 
 // ResNet stem: 7x7 stride-2 pad-3 convolution, 3 -> 64 channels, NHWC bf16 (stem.hip).
 // x4 = input padded to 4 channels; wp = weights packed [64][7 kh][8 kw][4 c] (zero padded).

@@ -27,7 +27,7 @@ from .._lib import buf_ok, hip, hip_available
 
 _ENABLED = os.environ.get("KUNGFU_CONV3X3", "1") != "0"
 _WGRAD = os.environ.get("KUNGFU_WGRAD", "1") != "0"
-_WGRAD_MAX_PIXELS = 1 << 31  # test hook; the kernels' own cap: hip().conv_wgrad_max_pixels
+_WGRAD_MAX_PIXELS = 1 << 31  # test hook; the kernels' own cap comes with hip().conv_wgrad_route
 
 
 def set_wgrad_enabled(on: bool) -> bool:
@@ -41,31 +41,38 @@ def _cl4(t: torch.Tensor) -> bool:
     return t.dim() == 4 and t.dtype == torch.bfloat16 and t.is_contiguous(memory_format=torch.channels_last)
 
 
-def wgrad(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, stride: int, pad: int) -> torch.Tensor:
-    """Weight gradient of ``F.conv2d(x, w, stride=stride, padding=pad)`` (bf16, w's shape).
+def wgrad(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, stride: int, pad) -> torch.Tensor:
+    """Weight gradient of ``F.conv2d(x, w, stride=stride, padding=pad)`` (bf16, w's shape); ``pad``: an
+    int or ``(ph, pw)``.
 
-    The MFMA split-K kernel for NHWC bf16 1x1 / 3x3 (pad (ks-1)/2) convolutions with
-    channel counts that are multiples of 64; MIOpen otherwise."""
-    ks = int(w.shape[2])
-    if (_WGRAD and x.is_cuda and _cl4(x) and _cl4(dy) and w.dim() == 4 and w.shape[3] == ks
-            and pad == (ks - 1) // 2 and hip_available()
-            and hip().conv_wgrad_supported(int(x.shape[1]), int(dy.shape[1]), ks, int(stride))):
-        n = int(x.shape[0])
+    NHWC bf16 tensors go where the planner's route says (csrc/kernels/wgrad_plan.cpp
+    ``conv_wgrad_route``): the "square" family ``_hip.conv_wgrad`` (1x1 / 3x3-pad-1, channels % 64), the
+    "rect" family ``_hip.conv_wgrad_rect`` (any window, channels % 8), or the library (MIOpen)."""
+    stride = int(stride)
+    ph, pw = _pair(pad)
+    route = "library"
+    if _WGRAD and x.is_cuda and _cl4(x) and _cl4(dy) and w.dim() == 4 and hip_available():
+        n, kh, kw = int(x.shape[0]), int(w.shape[2]), int(w.shape[3])
+        route, variant, cap = hip().conv_wgrad_route(n, int(x.shape[2]), int(x.shape[3]), int(x.shape[1]),
+                                                     int(dy.shape[1]), kh, kw, ph, pw, stride)
+    if route == "rect" and _WGRAD_RECT:
+        return hip().conv_wgrad_rect(dy, x, kh, kw, stride, ph, pw, variant)
+    if route == "square":
         per_img = int(dy.shape[2]) * int(dy.shape[3])
-        cap = min(_WGRAD_MAX_PIXELS, hip().conv_wgrad_max_pixels(n, int(x.shape[2]), int(x.shape[3]), int(x.shape[1]),
-                                                                 int(dy.shape[1]), ks, int(stride)))
+        cap = min(_WGRAD_MAX_PIXELS, cap)
         if n * per_img < cap:
-            return hip().conv_wgrad(dy, x, ks, int(stride))
-        # the tap-tiled kernel's pixel index math holds < 2^23 output pixels per launch: sum over
-        # batch chunks into one f32 gradient (the row-image 3x3 kernel has no such cap)
+            return hip().conv_wgrad(dy, x, kh, stride, variant=variant)
+        # past the kernel's pixels per launch (the tap-tiled kernel's index math holds < 2^23; the
+        # row-image 3x3 kernel has no such cap): sum over batch chunks, each planned for its own size,
+        # into one f32 gradient
         step = max(1, (cap - 1) // per_img)
         acc = torch.zeros(w.shape, dtype=torch.float32, device=x.device).contiguous(
             memory_format=torch.channels_last)
         for i in range(0, n, step):
-            hip().conv_wgrad(dy[i:i + step], x[i:i + step], ks, int(stride), out=acc, accumulate=True,
+            hip().conv_wgrad(dy[i:i + step], x[i:i + step], kh, stride, out=acc, accumulate=True,
                              atomics=False)  # deterministic (split-K partials + reduce)
         return acc.to(torch.bfloat16)
-    return torch.ops.aten.convolution_backward(dy, x, w, None, [stride, stride], [pad, pad], [1, 1], False, [0, 0], 1,
+    return torch.ops.aten.convolution_backward(dy, x, w, None, [stride, stride], [ph, pw], [1, 1], False, [0, 0], 1,
                                                [False, True, False])[1]
 
 
@@ -179,8 +186,7 @@ def rect_eligible(x: torch.Tensor, w: torch.Tensor, stride, padding, dilation, g
 class _ConvRectFn(torch.autograd.Function):
     """KH x KW convolution on the MFMA kernel (``_hip.conv_rect``).  Backward: stride 1 data
     gradient = the same kernel on the flipped weights with padding (KH-1-ph, KW-1-pw); stride 2
-    via MIOpen; weight gradient on the split-K MFMA kernel (:func:`wgrad` for the ResNet-shaped
-    1x1 / 3x3-pad-1 ones, ``_hip.conv_wgrad_rect`` for any other window / channel count).
+    via MIOpen; weight gradient through :func:`wgrad` (the split-K MFMA kernels the planner routes to).
     ``stats``: the BN statistics workspace of a following BN (epilogue sums, see ``bn_act``)."""
 
     @staticmethod
@@ -218,7 +224,7 @@ class _ConvRectFn(torch.autograd.Function):
                 dx = torch.ops.aten.convolution_backward(dy, x, w, None, [s, s], [ph, pw], [1, 1], False, [0, 0], 1,
                                                          [True, False, False])[0]
         if ctx.needs_input_grad[1]:
-            dw = _rect_wgrad(dy, x, w, s, ph, pw)
+            dw = wgrad(dy, x, w, s, (ph, pw))
         return dx, dw, None, None, None, None, None
 
 
@@ -231,37 +237,6 @@ def _dgrad_link(dy, wt, ph, pw, out, link):
     dx = hip().conv_rect(dy, wt, 1, ph, pw, link.ws, out, link.y, link.coef)
     link.ready, link.dx_ptr = True, dx.data_ptr()
     return dx
-
-
-def _rect_wgrad(dy, x, w, s, ph, pw):
-    """Weight gradient of a KH x KW convolution: the ResNet-tuned planner for 1x1 / 3x3-pad-1 with
-    channels % 64, the runtime-window split-K kernel for other wide layers, MIOpen for narrow ones."""
-    kh, kw = int(w.shape[2]), int(w.shape[3])
-    cin, cout = int(x.shape[1]), int(dy.shape[1])
-    if kh == kw and ph == pw == (kh - 1) // 2 and cin % 64 == 0 and cout % 64 == 0:
-        return wgrad(dy, x, w, s, ph)  # ResNet-tuned planner (row-image 3x3 kernel etc.)
-    # measured per Inception-v3 shape (tools/bench_inception_wgrad.py, profiles/r3q_inception_wgrad.txt):
-    # the split-K kernel wins every 1x1 (2-3x) and the multi-tap windows over >= 256 input
-    # channels; the narrow stride-1 multi-tap ones (32..192 inputs) take the row-image kernel
-    # (all taps of a workgroup share one staged input image: 54x54 80->192 3x3 992 -> 405 us,
-    # 111x111 32->32 3x3 438 -> 167 us on 32-channel tiles, 12x12 160->160 1x7 79 -> 55 us vs
-    # MIOpen, profiles/r5_inception_wgrad.md)
-    if (_WGRAD and _WGRAD_RECT and s == 1 and kh * kw > 1 and cin <= 192
-            and hip().conv_wgrad_rows_rect_supported(int(x.shape[0]), int(x.shape[2]), int(x.shape[3]), cin, cout,
-                                                     kh, kw, ph, pw, 1)):
-        return hip().conv_wgrad_rect(dy, x, kh, kw, 1, ph, pw, 13)  # 13: the per-shape row-image variant
-    if (_WGRAD and _WGRAD_RECT and s == 2 and kh * kw > 1
-            and hip().conv_wgrad_rows_rect_supported(int(x.shape[0]), int(x.shape[2]), int(x.shape[3]), cin, cout,
-                                                     kh, kw, ph, pw, 2)):
-        # the stride-2 windows (Mixed_6a / 7a reductions) on the row-image ring variants: 96->96 on
-        # 25x25 34 vs MIOpen 50 us, 288->384 241 vs 266 tap-tiled (profiles/r5_inception_wgrad.md)
-        return hip().conv_wgrad_rect(dy, x, kh, kw, 2, ph, pw, 13)
-    wide = kh * kw == 1 or cin % 128 == 0 or cin >= 256
-    if (_WGRAD and _WGRAD_RECT and wide and min(cin, cout) >= 32 and hip().conv_wgrad_rect_supported(cin, cout, kh, kw, s)
-            and int(dy.shape[0]) * int(dy.shape[2]) * int(dy.shape[3]) < (1 << 23)):
-        return hip().conv_wgrad_rect(dy, x, kh, kw, s, ph, pw)
-    return torch.ops.aten.convolution_backward(dy, x, w, None, [s, s], [ph, pw], [1, 1], False, [0, 0], 1,
-                                               [False, True, False])[1]
 
 
 class _SiblingConvFn(torch.autograd.Function):
@@ -296,7 +271,7 @@ class _SiblingConvFn(torch.autograd.Function):
                 kh, kw = int(w.shape[2]), int(w.shape[3])
                 # dx += (first: =); the last one completes dx, so its epilogue may take the BN sums
                 dx = _dgrad_link(dy, wt, kh - 1 - ph, kw - 1 - pw, dx, ctx.link if i == last else None)
-            dws.append(_rect_wgrad(dy, x, w, 1, ph, pw))
+            dws.append(wgrad(dy, x, w, 1, (ph, pw)))
         return (dx, None, None, None, *dws)
 
 
