@@ -164,3 +164,85 @@ def assert_bits_equal(got: torch.Tensor, ref_f64: torch.Tensor, what: str = "", 
     lines = ["%s  got %r  expected %r" % (tuple(i.tolist()), g[tuple(i)].item(), exp[tuple(i)].item()) for i in idx]
     raise AssertionError("%s: %d of %d elements differ from the exact reference; first:\n  %s" % (
         what, n, g.numel(), "\n  ".join(lines)))
+
+
+# ---- element-wise checks of kernels that round a value they know only to within delta -----------
+#
+# The BN apply kernels compute a handful of f32 operations per element and round once to bf16.
+# With general (non-integer) coefficients the f32 value is not exact, but it lies within
+# delta = 2^-24 * k * (sum of the magnitudes of the terms) of the f64 value of the same formula
+# (k = the f32 roundings on the path).  Rounding is monotone, so the stored value lies between
+# RNE(ref - delta) and RNE(ref + delta) -- for almost every element one and the same number.
+
+_SIG_BITS = {torch.bfloat16: 8, torch.float32: 24}
+_MIN_EXP = -125  # frexp exponent of the smallest normal f32 / bf16 (2^-126 = 0.5 * 2^-125)
+
+
+def ulp_of(v_f64: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """Spacing of ``dtype`` (bf16 / f32) at each |v|, in float64 (the subnormal spacing below the
+    smallest normal number)."""
+    _, e = torch.frexp(v_f64.abs())
+    e = e.clamp_min(_MIN_EXP).to(torch.float64)
+    return torch.exp2(e - _SIG_BITS[dtype])
+
+
+def round_to(v_f64: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """``v`` rounded to nearest-even in ``dtype`` (bf16 / f32), computed and returned in float64:
+    |v| in units of the target ulp (an exact power-of-two scaling), its floor and its fraction.  One
+    rounding -- ``v.float().bfloat16()`` rounds twice and merges values closer than an f32 ulp."""
+    assert v_f64.dtype == torch.float64
+    ulp = ulp_of(v_f64, dtype)
+    t = v_f64.abs() / ulp
+    fl = torch.floor(t)
+    frac = t - fl
+    up = (frac > 0.5) | ((frac == 0.5) & (torch.remainder(fl, 2) == 1))
+    return torch.copysign((fl + up.to(torch.float64)) * ulp, v_f64)
+
+
+def rounding_interval(ref_f64: torch.Tensor, delta_f64: torch.Tensor, dtype: torch.dtype, relu: bool = False):
+    """(lo, hi, ambiguous): the ``dtype`` values between which a kernel's output must lie when it
+    rounds (after a ReLU when ``relu``) an f32 value within ``delta`` of ``ref``; ``ambiguous`` where
+    lo != hi, i.e. where [ref - delta, ref + delta] holds a rounding boundary (or, with a ReLU, 0)."""
+    a, b = ref_f64 - delta_f64, ref_f64 + delta_f64
+    if relu:
+        a, b = a.clamp_min(0), b.clamp_min(0)
+    lo, hi = round_to(a, dtype), round_to(b, dtype)
+    return lo, hi, lo != hi
+
+
+def assert_rounds_from(got: torch.Tensor, ref_f64: torch.Tensor, delta_f64, what: str = "",
+                       max_ambiguous: float = 0.01, relu: bool = False) -> torch.Tensor:
+    """``got`` (bf16 / f32) is one rounding away from a value the kernel knows to within ``delta`` of
+    ``ref_f64`` (with ``relu``: ``ref_f64`` is the value before a ReLU that precedes the rounding).
+    Every element must equal RNE(ref) in ``got.dtype``; only where [ref - delta, ref + delta] straddles
+    a rounding boundary may it be either neighbour (with a ReLU and 0 inside the interval: 0 or the
+    neighbour).  The share of such ambiguous elements is asserted, on the reference alone, to be at
+    most ``max_ambiguous``: a condition on the data recipe, not a measurement of the kernel.  A
+    mismatch reports the count, the first indices ([n, c, h, w] for a 4-D tensor) and got / expected.
+    Returns the bool tensor of ambiguous elements."""
+    assert ref_f64.dtype == torch.float64, "%s: the reference must be float64" % what
+    assert got.dtype in _SIG_BITS, "%s: %s output" % (what, got.dtype)
+    assert tuple(got.shape) == tuple(ref_f64.shape), "%s: shape %s vs reference %s" % (
+        what, tuple(got.shape), tuple(ref_f64.shape))
+    ref = ref_f64.to(got.device)
+    delta = torch.as_tensor(delta_f64, dtype=torch.float64, device=got.device).expand_as(ref)
+    assert torch.isfinite(ref).all() and torch.isfinite(delta).all() and (delta >= 0).all(), \
+        "%s: non-finite reference or delta" % what
+    lo, hi, amb = rounding_interval(ref, delta, got.dtype, relu)
+    share = amb.double().mean().item() if amb.numel() else 0.0
+    assert share <= max_ambiguous, "%s: %.3g of the reference elements are ambiguous (cap %.3g): " \
+        "the data recipe does not suit this check" % (what, share, max_ambiguous)
+    g = got.detach().double()
+    bad = ~((g >= lo) & (g <= hi))  # a NaN fails both comparisons
+    n = int(bad.sum().item())
+    if n:
+        exp = round_to(ref.clamp_min(0) if relu else ref, got.dtype)
+        idx = bad.nonzero()[:8].cpu()
+        lines = []
+        for i in idx:
+            i = tuple(i.tolist())
+            e = "%r" % exp[i].item() if not amb[i].item() else "%r..%r" % (lo[i].item(), hi[i].item())
+            lines.append("%s  got %r  expected %s" % (i, g[i].item(), e))
+        raise AssertionError("%s: %d of %d elements are not the rounded reference; first:\n  %s" % (
+            what, n, g.numel(), "\n  ".join(lines)))
+    return amb

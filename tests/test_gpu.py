@@ -141,6 +141,8 @@ def test_pack_unpack(H):
                                    (2, 384, 5, 7)])
 @pytest.mark.parametrize("relu,with_res", [(True, False), (True, True), (False, False)])
 def test_fused_bn(shape, relu, with_res):
+    """bn_act forward and backward through autograd vs f32 torch, max|err| / max|ref| < 3e-2.
+    The element-wise float64 checks of the same kernels are in tests/test_gpu_bn_exact.py."""
     import torch.nn.functional as F
 
     from kungfu_amd.ops.fused_bn import bn_act
