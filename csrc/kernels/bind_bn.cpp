@@ -1,6 +1,7 @@
 // Fused NHWC BatchNorm (+residual, +ReLU, +MaxPool) forward / backward.
 #include "bind_util.hpp"
 
+#include <string>
 #include <vector>
 
 using namespace kfb;
@@ -16,29 +17,66 @@ kfk::BNShape bn_shape(const at::Tensor &x, const char *op) {
     return kfk::BNShape{x.numel() / C, C};
 }
 
-struct BNCommon {
-    float *rm = nullptr, *rv = nullptr;
-    int64_t *nbt = nullptr;
-};
-
-BNCommon bn_common(const char *op, int C, const Dev &dev, const at::Tensor &weight, const at::Tensor &bias,
-                   const OptTensor &running_mean, const OptTensor &running_var, const OptTensor &num_batches,
-                   bool training) {
-    check_dense(weight, op, "weight", dev, at::kFloat, C);
-    check_dense(bias, op, "bias", dev, at::kFloat, C);
-    BNCommon b;
+// The checked parameters of one BN as the forward descriptor: everything but the outputs, sums and partial.
+kfk::BnFinDesc bn_common(const char *op, kfk::BNShape sh, const Dev &dev, const at::Tensor &weight,
+                         const at::Tensor &bias, const OptTensor &running_mean, const OptTensor &running_var,
+                         const OptTensor &num_batches, bool training, double momentum, double eps) {
+    check_dense(weight, op, "weight", dev, at::kFloat, sh.channels);
+    check_dense(bias, op, "bias", dev, at::kFloat, sh.channels);
+    kfk::BnFinDesc d;
+    d.rows = sh.rows, d.C = sh.channels;
+    d.gamma = weight.data_ptr<float>(), d.beta = bias.data_ptr<float>();
+    d.momentum = static_cast<float>(momentum), d.eps = static_cast<float>(eps);
     if (has(running_mean)) {
         TORCH_CHECK(has(running_var), op, ": running_var missing");
-        b.rm = running_mean->data_ptr<float>();
-        b.rv = running_var->data_ptr<float>();
+        d.run_mean = running_mean->data_ptr<float>();
+        d.run_var = running_var->data_ptr<float>();
     }
-    TORCH_CHECK(training || b.rm, op, ": eval mode needs running stats");
+    TORCH_CHECK(training || d.run_mean, op, ": eval mode needs running stats");
     if (training && has(num_batches)) {
         TORCH_CHECK(num_batches->scalar_type() == at::kLong && num_batches->numel() == 1 && num_batches->is_cuda(),
                     op, ": num_batches_tracked must be a 1-element int64 GPU tensor");
-        b.nbt = num_batches->data_ptr<int64_t>();
+        d.nbt = num_batches->data_ptr<int64_t>();
     }
-    return b;
+    return d;
+}
+
+// {mean, invstd, coef}: the forward's f32 outputs ([C], [C], [scale; shift] = [2C]); out_stats points d at them.
+std::vector<at::Tensor> alloc_stats(int C, const at::TensorOptions &fopt) {
+    return {at::empty({C}, fopt), at::empty({C}, fopt), at::empty({2 * C}, fopt)};
+}
+
+void out_stats(kfk::BnFinDesc &d, const std::vector<at::Tensor> &st) {
+    d.mean = st[0].data_ptr<float>(), d.invstd = st[1].data_ptr<float>(), d.coef = st[2].data_ptr<float>();
+}
+
+// The scratch of a statistics / reduce pass.
+at::Tensor alloc_partial(kfk::BNShape sh, const at::TensorOptions &fopt) {
+    return at::empty({2 * static_cast<int64_t>(kfk::bn_num_chunks(sh)) * sh.channels}, fopt);
+}
+
+// What a backward takes from its forward: mean / invstd / weight [C] and fcoef [2C], checked, as the
+// backward descriptor without its outputs.  `s`: "s" where the arguments are lists of them.
+kfk::BnBwdFinDesc bn_saved(const char *op, kfk::BNShape sh, const Dev &dev, const at::Tensor &mean,
+                           const at::Tensor &invstd, const at::Tensor &weight, const at::Tensor &fcoef,
+                           const char *s = "") {
+    const int C = sh.channels;
+    const auto name = [s](const char *n) { return std::string(n) + s; };
+    check_dense(mean, op, name("mean").c_str(), dev, at::kFloat, C);
+    check_dense(invstd, op, name("invstd").c_str(), dev, at::kFloat, C);
+    check_dense(weight, op, name("weight").c_str(), dev, at::kFloat, C);
+    check_dense(fcoef, op, name("fcoef").c_str(), dev, at::kFloat, 2 * C);
+    kfk::BnBwdFinDesc d;
+    d.rows = sh.rows, d.C = C;
+    d.gamma = weight.data_ptr<float>(), d.mean = mean.data_ptr<float>(), d.invstd = invstd.data_ptr<float>();
+    return d;
+}
+
+// {dweight, dbias, coef}: the backward's f32 outputs ([C], [C], [k1; k2; k3] = [3C]), d pointed at them.
+std::vector<at::Tensor> alloc_bwd_out(kfk::BnBwdFinDesc &d, const at::TensorOptions &fopt) {
+    std::vector<at::Tensor> o{at::empty({d.C}, fopt), at::empty({d.C}, fopt), at::empty({3 * d.C}, fopt)};
+    d.dgamma = o[0].data_ptr<float>(), d.dbeta = o[1].data_ptr<float>(), d.coef = o[2].data_ptr<float>();
+    return o;
 }
 
 // The output gradient of a BN: x's shape, bf16, on its device.  Read in place when it is channels_last or a
@@ -77,27 +115,19 @@ std::vector<std::vector<at::Tensor>> bn_finalize_multi(std::vector<at::Tensor> x
                 "bn_finalize_multi: 1..8 BNs, every list of the same length");
     kfk::BnFinBatch b{};
     b.n = static_cast<int>(n);
+    const Dev dev = xs[0].device();
     for (size_t i = 0; i < n; ++i) {
         auto sh = bn_shape(xs[i], op);
-        const Dev dev = xs[0].device();
         TORCH_CHECK(xs[i].device() == *dev, "bn_finalize_multi: xs must be on one device");
-        auto c = bn_common(op, sh.channels, dev, weights[i], biases[i], running_means[i], running_vars[i],
-                           num_batches[i], true);
-        kfk::BnFinDesc &d = b.d[i];
+        b.d[i] = bn_common(op, sh, dev, weights[i], biases[i], running_means[i], running_vars[i], num_batches[i], true,
+                           momentum[i], eps[i]);
         TORCH_CHECK(sums[i].defined(), "bn_finalize_multi: sums must be defined");
-        d.sums = stats_ptr(sums[i], op, sh.channels, dev, "sums");
-        d.gamma = weights[i].data_ptr<float>(), d.beta = biases[i].data_ptr<float>();
-        d.run_mean = c.rm, d.run_var = c.rv, d.nbt = c.nbt;
-        d.rows = sh.rows, d.C = sh.channels;
-        d.momentum = static_cast<float>(momentum[i]), d.eps = static_cast<float>(eps[i]);
+        b.d[i].sums = stats_ptr(sums[i], op, sh.channels, dev, "sums");
     }
     std::vector<std::vector<at::Tensor>> out;
     for (size_t i = 0; i < n; ++i) {
-        kfk::BnFinDesc &d = b.d[i];
-        auto fopt = xs[i].options().dtype(at::kFloat);
-        at::Tensor mean = at::empty({d.C}, fopt), invstd = at::empty({d.C}, fopt), coef = at::empty({2 * d.C}, fopt);
-        d.mean = mean.data_ptr<float>(), d.invstd = invstd.data_ptr<float>(), d.coef = coef.data_ptr<float>();
-        out.push_back({mean, invstd, coef});
+        out.push_back(alloc_stats(b.d[i].C, xs[i].options().dtype(at::kFloat)));
+        out_stats(b.d[i], out.back());
     }
     c10::DeviceGuard gd(xs[0].device());
     kfk::launch_bn_sums_finalize_multi(b, stream_of(xs[0], 0));
@@ -113,59 +143,59 @@ std::vector<at::Tensor> bn_forward(at::Tensor x, OptTensor res, at::Tensor weigh
     auto sh = bn_shape(x, op);
     const int C = sh.channels;
     const Dev dev = x.device();
-    auto b = bn_common(op, C, dev, weight, bias, running_mean, running_var, num_batches, training);
-    const uint16_t *rp = nullptr;
+    kfk::BnForwardArgs a;
+    a.bn = bn_common(op, sh, dev, weight, bias, running_mean, running_var, num_batches, training, momentum, eps);
+    a.x = bf16(x), a.training = training, a.relu = relu, a.apply = apply;
     if (has(res)) {
         check_cl4(*res, op, "res", dev, x.sizes());
-        rp = bf16(*res);
+        a.res = bf16(*res);
     }
-    const float *rc = nullptr;
     if (has(res_coef)) {
-        TORCH_CHECK(rp, "bn_forward: res_coef (the residual BN's f32 [scale(C); shift(C)]) needs res");
+        TORCH_CHECK(a.res, "bn_forward: res_coef (the residual BN's f32 [scale(C); shift(C)]) needs res");
         check_dense(*res_coef, op, "res_coef", dev, at::kFloat, 2 * C);
-        rc = res_coef->data_ptr<float>();
+        a.res_coef = res_coef->data_ptr<float>();
     }
-    int64_t y_ld = 0;
     if (has(out)) {
         // a channel slice [N, C, H, W] of a wider channels_last bf16 tensor (a concatenation)
-        TORCH_CHECK(apply && !rp && relu && out->scalar_type() == at::kBFloat16 && out->sizes() == x.sizes() &&
+        TORCH_CHECK(apply && !a.res && relu && out->scalar_type() == at::kBFloat16 && out->sizes() == x.sizes() &&
                         out->stride(1) == 1 && out->stride(3) >= C && out->stride(3) % 8 == 0 &&
                         out->stride(2) == out->size(3) * out->stride(3) &&
                         out->stride(0) == out->size(2) * out->stride(2) &&
                         reinterpret_cast<uintptr_t>(out->data_ptr()) % 16 == 0 && out->device() == x.device(),
                     "bn_forward: out must be a 16-byte aligned channel slice of a channels_last bf16 tensor "
                     "(BN+ReLU, no residual)");
-        y_ld = out->stride(3);
+        a.y_ld = out->stride(3);
     }
-    const bool prefin = pre.has_value();
-    if (prefin) {
+    a.prefinalized = pre.has_value();
+    if (a.prefinalized) {
         // (mean, invstd, coef) already written from `sums` by the batched bn_finalize_multi launch
         TORCH_CHECK(pre->size() == 3 && training && has(sums), "bn_forward: pre must be (mean, invstd, coef) with sums");
         check_dense((*pre)[0], op, "pre[0]", dev, at::kFloat, C);
         check_dense((*pre)[1], op, "pre[1]", dev, at::kFloat, C);
         check_dense((*pre)[2], op, "pre[2]", dev, at::kFloat, 2 * C);
     }
-    double *sp = training ? stats_ptr(sums, op, C, dev, "sums") : nullptr;
+    if (training) a.bn.sums = stats_ptr(sums, op, C, dev, "sums");
 
     c10::DeviceGuard gd(x.device());
     auto fopt = x.options().dtype(at::kFloat);
     at::Tensor y;
     if (has(out)) y = *out;
     else if (apply) y = at::empty_like(x, kCL);
-    at::Tensor mean, invstd, coef;
-    if (prefin) mean = (*pre)[0], invstd = (*pre)[1], coef = (*pre)[2];
-    else mean = at::empty({C}, fopt), invstd = at::empty({C}, fopt), coef = at::empty({2 * C}, fopt);
+    if (apply) a.y = bf16_mut(y);
+    const std::vector<at::Tensor> st = a.prefinalized ? *pre : alloc_stats(C, fopt);
+    out_stats(a.bn, st);
     at::Tensor mask;
-    if (apply && rp && relu) mask = at::empty({sh.rows * (C / 8)}, x.options().dtype(at::kByte));
+    if (apply && a.res && relu) {
+        mask = at::empty({sh.rows * (C / 8)}, x.options().dtype(at::kByte));
+        a.mask = mask.data_ptr<uint8_t>();
+    }
     at::Tensor partial;
-    if (training && !sp) partial = at::empty({2 * static_cast<int64_t>(kfk::bn_num_chunks(sh)) * C}, fopt);
-    kfk::launch_bn_forward(bf16(x), rp, weight.data_ptr<float>(), bias.data_ptr<float>(),
-                           apply ? bf16_mut(y) : nullptr, mask.defined() ? mask.data_ptr<uint8_t>() : nullptr, sh, relu,
-                           training, b.rm, b.rv, static_cast<float>(momentum), static_cast<float>(eps),
-                           partial.defined() ? partial.data_ptr<float>() : nullptr, mean.data_ptr<float>(),
-                           invstd.data_ptr<float>(), coef.data_ptr<float>(), b.nbt, stream_of(x, 0), sp, rc, apply, y_ld,
-                           prefin);
-    return {y, mean, invstd, coef, mask};
+    if (training && !a.bn.sums) {
+        partial = alloc_partial(sh, fopt);
+        a.bn.partial = partial.data_ptr<float>();
+    }
+    kfk::launch_bn_forward(a, stream_of(x, 0));
+    return {y, st[0], st[1], st[2], mask};
 }
 
 // Returns (dx, dres or undefined, dweight, dbias).
@@ -177,41 +207,41 @@ std::vector<at::Tensor> bn_backward(at::Tensor dy, at::Tensor x, at::Tensor mean
     const int C = sh.channels;
     const Dev dev = x.device();
     check_bn_dy(dy, x, op);
-    check_dense(mean, op, "mean", dev, at::kFloat, C);
-    check_dense(invstd, op, "invstd", dev, at::kFloat, C);
-    check_dense(weight, op, "weight", dev, at::kFloat, C);
-    check_dense(fcoef, op, "fcoef", dev, at::kFloat, 2 * C);
-    const uint8_t *mp = nullptr;
+    kfk::BnBackwardArgs a;
+    a.bn = bn_saved(op, sh, dev, mean, invstd, weight, fcoef);
+    a.bn.training = training;
+    a.x = bf16(x), a.fcoef = fcoef.data_ptr<float>(), a.relu = relu;
     if (has(mask)) {
         check_dense(*mask, op, "mask", dev, at::kByte, sh.rows * (C / 8));
-        mp = mask->data_ptr<uint8_t>();
+        a.mask = mask->data_ptr<uint8_t>();
     }
-    double *sp = stats_ptr(sums, op, C, dev, "sums");
-    const uint16_t *dsx = nullptr;
-    double *dsp = nullptr;
+    a.bn.sums = stats_ptr(sums, op, C, dev, "sums");
     if (has(dres_x)) {
         TORCH_CHECK(want_dres && has(dres_sums),
                     "bn_backward: dres_x (second BN's input) needs want_dres and its f64 sums workspace dres_sums");
         check_cl4(*dres_x, op, "dres_x", dev, x.sizes());
-        dsx = bf16(*dres_x);
-        dsp = stats_ptr(dres_sums, op, C, dev, "dres_sums");
+        a.dres_x = bf16(*dres_x);
+        a.dres_sums = stats_ptr(dres_sums, op, C, dev, "dres_sums");
     }
     c10::DeviceGuard gd(x.device());
-    int64_t dy_ld;
-    dy = bn_dy(dy, x, C, &dy_ld);
+    dy = bn_dy(dy, x, C, &a.dy_ld);
+    a.dy = bf16(dy);
     auto fopt = x.options().dtype(at::kFloat);
     auto dx = at::empty_like(x, kCL);
+    a.dx = bf16_mut(dx);
     at::Tensor dres;
-    if (want_dres) dres = at::empty_like(x, kCL);
-    at::Tensor dw = at::empty({C}, fopt), db = at::empty({C}, fopt), coef = at::empty({3 * C}, fopt);
+    if (want_dres) {
+        dres = at::empty_like(x, kCL);
+        a.dres = bf16_mut(dres);
+    }
+    const auto o = alloc_bwd_out(a.bn, fopt);
     at::Tensor partial;
-    if (!sp) partial = at::empty({2 * static_cast<int64_t>(kfk::bn_num_chunks(sh)) * C}, fopt);
-    kfk::launch_bn_backward(bf16(dy), bf16(x), fcoef.data_ptr<float>(), mp, mean.data_ptr<float>(),
-                            invstd.data_ptr<float>(), weight.data_ptr<float>(), sh, relu, training,
-                            partial.defined() ? partial.data_ptr<float>() : nullptr, dw.data_ptr<float>(),
-                            db.data_ptr<float>(), coef.data_ptr<float>(), bf16_mut(dx),
-                            want_dres ? bf16_mut(dres) : nullptr, stream_of(x, 0), sp, dsx, dsp, dy_ld);
-    return {dx, dres, dw, db};
+    if (!a.bn.sums) {
+        partial = alloc_partial(sh, fopt);
+        a.bn.partial = partial.data_ptr<float>();
+    }
+    kfk::launch_bn_backward(a, stream_of(x, 0));
+    return {dx, dres, o[0], o[1]};
 }
 
 // Backward of several training BN+ReLUs (no residual, no sums) whose output gradients may be channel
@@ -225,54 +255,39 @@ std::vector<std::vector<at::Tensor>> bn_backward_multi(std::vector<at::Tensor> d
     TORCH_CHECK(n >= 1 && n <= static_cast<size_t>(kfk::kBnFinMax) && dys.size() == n && means.size() == n &&
                     invstds.size() == n && weights.size() == n && fcoefs.size() == n,
                 "bn_backward_multi: 1..8 BNs, every list of the same length");
-    struct Piece {
-        at::Tensor dy, dx, dw, db, coef, partial;
-        int64_t ld;
-        kfk::BNShape sh;
-    };
-    std::vector<Piece> ps(n);
+    std::vector<kfk::BnBackwardArgs> as(n);
+    std::vector<kfk::BNShape> shs(n);
     const Dev dev = xs[0].device();
     for (size_t i = 0; i < n; ++i) {
-        ps[i].sh = bn_shape(xs[i], op);
-        const int C = ps[i].sh.channels;
+        shs[i] = bn_shape(xs[i], op);
         TORCH_CHECK(xs[i].device() == *dev, "bn_backward_multi: xs must be on one device");
         check_bn_dy(dys[i], xs[i], op);
-        check_dense(fcoefs[i], op, "fcoefs", dev, at::kFloat, 2 * C);
-        check_dense(means[i], op, "means", dev, at::kFloat, C);
-        check_dense(invstds[i], op, "invstds", dev, at::kFloat, C);
-        check_dense(weights[i], op, "weights", dev, at::kFloat, C);
+        as[i].bn = bn_saved(op, shs[i], dev, means[i], invstds[i], weights[i], fcoefs[i], "s");
+        as[i].x = bf16(xs[i]), as[i].fcoef = fcoefs[i].data_ptr<float>(), as[i].relu = true;
     }
     c10::DeviceGuard gd(xs[0].device());
+    std::vector<at::Tensor> keep;  // the gradients read (a copy where bn_dy made one) and the partials
+    std::vector<std::vector<at::Tensor>> out;
     kfk::BnBwdFinBatch fb{};
     fb.n = static_cast<int>(n);
     for (size_t i = 0; i < n; ++i) {
-        Piece &p = ps[i];
-        const int C = p.sh.channels;
-        p.dy = bn_dy(dys[i], xs[i], C, &p.ld);
+        kfk::BnBackwardArgs &a = as[i];
         auto fopt = xs[i].options().dtype(at::kFloat);
-        p.dx = at::empty_like(xs[i], kCL);
-        p.dw = at::empty({C}, fopt), p.db = at::empty({C}, fopt), p.coef = at::empty({3 * C}, fopt);
-        p.partial = at::empty({2 * static_cast<int64_t>(kfk::bn_num_chunks(p.sh)) * C}, fopt);
-        kfk::BnBwdFinDesc &d = fb.d[i];
-        d.partial = p.partial.data_ptr<float>();
-        d.nchunks = kfk::bn_num_chunks(p.sh), d.C = C, d.rows = p.sh.rows;
-        d.gamma = weights[i].data_ptr<float>(), d.mean = means[i].data_ptr<float>(), d.invstd = invstds[i].data_ptr<float>();
-        d.dgamma = p.dw.data_ptr<float>(), d.dbeta = p.db.data_ptr<float>(), d.coef = p.coef.data_ptr<float>();
+        keep.push_back(bn_dy(dys[i], xs[i], a.bn.C, &a.dy_ld));
+        a.dy = bf16(keep.back());
+        auto dx = at::empty_like(xs[i], kCL);
+        a.dx = bf16_mut(dx);
+        const auto o = alloc_bwd_out(a.bn, fopt);
+        keep.push_back(alloc_partial(shs[i], fopt));
+        a.bn.partial = keep.back().data_ptr<float>();
+        fb.d[i] = a.bn;
+        out.push_back({dx, o[0], o[1]});
+        keep.push_back(o[2]);
     }
     const hipStream_t st = stream_of(xs[0], 0);
-    for (int phase : {1, 2}) {
-        if (phase == 2) kfk::launch_bn_bwd_finalize_multi(fb, st);
-        for (size_t i = 0; i < n; ++i) {
-            Piece &p = ps[i];
-            kfk::launch_bn_backward(bf16(p.dy), bf16(xs[i]), fcoefs[i].data_ptr<float>(), nullptr,
-                                    means[i].data_ptr<float>(), invstds[i].data_ptr<float>(),
-                                    weights[i].data_ptr<float>(), p.sh, true, true, p.partial.data_ptr<float>(),
-                                    p.dw.data_ptr<float>(), p.db.data_ptr<float>(), p.coef.data_ptr<float>(),
-                                    bf16_mut(p.dx), nullptr, st, nullptr, nullptr, nullptr, p.ld, phase);
-        }
-    }
-    std::vector<std::vector<at::Tensor>> out;
-    for (auto &p : ps) out.push_back({p.dx, p.dw, p.db});
+    for (auto &a : as) kfk::launch_bn_backward_reduce(a, st);
+    kfk::launch_bn_bwd_finalize_multi(fb, st);
+    for (auto &a : as) kfk::launch_bn_backward_apply(a, st);
     return out;
 }
 
@@ -284,27 +299,29 @@ std::vector<at::Tensor> bn_pool_forward(at::Tensor x, at::Tensor weight, at::Ten
     auto sh = bn_shape(x, op);
     const int C = sh.channels;
     const Dev dev = x.device();
-    const int H = narrow(x.size(2), op, "x"), W = narrow(x.size(3), op, "x");
-    TORCH_CHECK(kfk::bn_pool_supported(sh, H, W), "bn_pool_forward: unsupported shape");
+    kfk::BnPoolForwardArgs a;
+    a.H = narrow(x.size(2), op, "x"), a.W = narrow(x.size(3), op, "x");
+    TORCH_CHECK(kfk::bn_pool_supported(sh, a.H, a.W), "bn_pool_forward: unsupported shape");
     double *sp = training ? stats_ptr(sums, op, C, dev, "sums") : nullptr;
-    auto b = bn_common(op, C, dev, weight, bias, running_mean, running_var, num_batches, training);
+    a.bn = bn_common(op, sh, dev, weight, bias, running_mean, running_var, num_batches, training, momentum, eps);
+    a.bn.sums = sp;
+    a.x = bf16(x), a.training = training;
     c10::DeviceGuard gd(x.device());
     auto fopt = x.options().dtype(at::kFloat);
-    const int OH = kfk::pool_out(H), OW = kfk::pool_out(W);
+    const int OH = kfk::pool_out(a.H), OW = kfk::pool_out(a.W);
     auto yp = at::empty({x.size(0), C, OH, OW}, x.options().memory_format(kCL));
     auto arg = at::empty({x.size(0) * OH * OW * C}, x.options().dtype(at::kByte));
-    auto mean = at::empty({C}, fopt), invstd = at::empty({C}, fopt), coef = at::empty({2 * C}, fopt);
+    a.yp = bf16_mut(yp), a.arg = arg.data_ptr<uint8_t>();
+    const auto st = alloc_stats(C, fopt);
+    out_stats(a.bn, st);
     at::Tensor partial, xarg;
     if (training) {
-        partial = at::empty({2 * static_cast<int64_t>(kfk::bn_num_chunks(sh)) * C}, fopt);
+        partial = alloc_partial(sh, fopt);
         xarg = at::empty_like(yp, kCL);
+        a.bn.partial = partial.data_ptr<float>(), a.xarg = bf16_mut(xarg);
     }
-    kfk::launch_bn_pool_forward(bf16(x), weight.data_ptr<float>(), bias.data_ptr<float>(), bf16_mut(yp),
-                                arg.data_ptr<uint8_t>(), sh, H, W, training, b.rm, b.rv, static_cast<float>(momentum),
-                                static_cast<float>(eps), training ? partial.data_ptr<float>() : nullptr,
-                                mean.data_ptr<float>(), invstd.data_ptr<float>(), coef.data_ptr<float>(), b.nbt,
-                                stream_of(x, 0), sp, xarg.defined() ? bf16_mut(xarg) : nullptr);
-    return {yp, mean, invstd, coef, arg, xarg};
+    kfk::launch_bn_pool_forward(a, stream_of(x, 0));
+    return {yp, st[0], st[1], st[2], arg, xarg};
 }
 
 // Returns (dx, dweight, dbias).
@@ -315,33 +332,38 @@ std::vector<at::Tensor> bn_pool_backward(at::Tensor dyp, at::Tensor arg, at::Ten
     auto sh = bn_shape(x, op);
     const int C = sh.channels;
     const Dev dev = x.device();
-    const int H = narrow(x.size(2), op, "x"), W = narrow(x.size(3), op, "x");
-    const int64_t psz[4] = {x.size(0), C, kfk::pool_out(H), kfk::pool_out(W)};
+    kfk::BnPoolBackwardArgs a;
+    a.H = narrow(x.size(2), op, "x"), a.W = narrow(x.size(3), op, "x");
+    const int64_t psz[4] = {x.size(0), C, kfk::pool_out(a.H), kfk::pool_out(a.W)};
     TORCH_CHECK(dyp.scalar_type() == at::kBFloat16 && dyp.sizes() == at::IntArrayRef(psz) && dyp.device() == x.device(),
                 "bn_pool_backward: dy must be the pooled [N, C, PH, PW] bf16 gradient on x's device");
     check_dense(arg, op, "arg", dev, at::kByte, dyp.numel());
-    check_dense(mean, op, "mean", dev, at::kFloat, C);
-    check_dense(invstd, op, "invstd", dev, at::kFloat, C);
-    check_dense(weight, op, "weight", dev, at::kFloat, C);
-    check_dense(fcoef, op, "fcoef", dev, at::kFloat, 2 * C);
+    a.bn = bn_saved(op, sh, dev, mean, invstd, weight, fcoef);
+    a.bn.training = training;
+    a.arg = arg.data_ptr<uint8_t>(), a.x = bf16(x), a.fcoef = fcoef.data_ptr<float>(), a.apply = apply;
     const bool pooled = training && has(xarg);
-    if (pooled) check_cl4(*xarg, op, "xarg", dev, psz);
+    if (pooled) {
+        check_cl4(*xarg, op, "xarg", dev, psz);
+        a.xarg = bf16(*xarg);
+    }
     c10::DeviceGuard gd(x.device());
     if (!dyp.is_contiguous(kCL)) dyp = dyp.contiguous(kCL);
+    a.dyp = bf16(dyp);
     auto fopt = x.options().dtype(at::kFloat);
     // apply = false: statistics + finalize only -- dx is not formed (an empty tensor), the backward
     // coefficients [k1; k2; k3] are returned for the caller's own pass (stem_wgrad_bnp)
     auto dx = apply ? at::empty_like(x, kCL) : at::empty({0}, x.options());
-    auto dw = at::empty({C}, fopt), db = at::empty({C}, fopt), coef = at::empty({3 * C}, fopt);
-    auto partial = at::empty({2 * static_cast<int64_t>(kfk::bn_num_chunks(sh)) * C}, fopt);
+    if (apply) a.dx = bf16_mut(dx);
+    const auto o = alloc_bwd_out(a.bn, fopt);
+    auto partial = alloc_partial(sh, fopt);
+    a.bn.partial = partial.data_ptr<float>();
     at::Tensor sums;
-    if (pooled) sums = at::zeros({2 * C * kfk::kStatSlots}, x.options().dtype(at::kDouble));
-    kfk::launch_bn_pool_backward(bf16(dyp), arg.data_ptr<uint8_t>(), bf16(x), fcoef.data_ptr<float>(),
-                                 mean.data_ptr<float>(), invstd.data_ptr<float>(), weight.data_ptr<float>(), sh, H, W,
-                                 training, partial.data_ptr<float>(), dw.data_ptr<float>(), db.data_ptr<float>(),
-                                 coef.data_ptr<float>(), apply ? bf16_mut(dx) : nullptr, stream_of(x, 0),
-                                 pooled ? bf16(*xarg) : nullptr, pooled ? sums.data_ptr<double>() : nullptr, apply);
-    return {dx, dw, db, coef};
+    if (pooled) {
+        sums = at::zeros({2 * C * kfk::kStatSlots}, x.options().dtype(at::kDouble));
+        a.bn.sums = sums.data_ptr<double>();
+    }
+    kfk::launch_bn_pool_backward(a, stream_of(x, 0));
+    return {dx, o[0], o[1], o[2]};
 }
 
 }  // namespace

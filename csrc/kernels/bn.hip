@@ -28,7 +28,6 @@
 //
 // Statistics are two-stage and deterministic: per-chunk partial sums (f32)
 // then a per-channel fold in f64 (no float atomics).
-#include "bn_fin.hpp"
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -225,106 +224,146 @@ __global__ __launch_bounds__(kBlock) void bn_stats_kernel(const uint4 *__restric
     reduce_to_partials<CVEC, 2>(acc, lds, partial, C, gridDim.x);
 }
 
-// Fold partials (parallel over chunks), emit mean/invstd, running stats and
-// the affine coefficients scale = gamma*invstd, shift = beta - mean*scale.
-__global__ __launch_bounds__(kBlock) void bn_stats_finalize(const float *partial, int nchunks, int C, int64_t rows,
-                                                            const float *gamma, const float *beta, float *mean,
-                                                            float *invstd, float *run_mean, float *run_var,
-                                                            float momentum, float eps, float *coef,
-                                                            int64_t *num_batches) {
-    const int c = blockIdx.x * kFoldCh + threadIdx.x % kFoldCh, kl = threadIdx.x / kFoldCh;
-    double sums[2];
-    fold_partials<2>(partial, nchunks, C, c, kl, sums);
-    if (num_batches && blockIdx.x == 0 && threadIdx.x == 0) num_batches[0] += 1;
-    if (kl != 0 || c >= C) return;
-    double s = sums[0], q = sums[1];
-    double m = s / rows;
+// ---------------------------------------------------------------- finalize
+//
+// Per channel, from f64 sums: the forward batch statistics / affine coefficients / running stats
+// (bn_fin_fwd_channel), or the backward dgamma / dbeta and the three backward-apply coefficients
+// (bn_fin_bwd_channel).  The sums come from the partials of a statistics / reduce pass or from the
+// kStatSlots f64 slots of a convolution epilogue: four bodies, each behind a single-BN kernel and,
+// where several BNs are finalized together, a batched one (blockIdx.y = which BN).  One definition
+// each, so the single and the batched kernels produce bit-identical results.
+
+// Sum the kStatSlots slots [2][C] of channel c and re-zero them for the next producer
+// (self-cleaning workspace, no memset launch).
+// every input issued before any store: the slot sums here, and in the callers the channel's
+// parameters / running stats (loaded behind the zeroing and output stores, each was a serial
+// round trip: 5.7 us)
+__device__ __forceinline__ void fold_slots(double *sums, int c, int C, double &s0, double &s1) {
+    double *sp = sums + c;
+    double v0[kStatSlots], v1[kStatSlots];
+#pragma unroll
+    for (int k = 0; k < kStatSlots; ++k) {
+        v0[k] = sp[k * 2 * C];
+        v1[k] = sp[k * 2 * C + C];
+    }
+    s0 = 0, s1 = 0;
+#pragma unroll
+    for (int k = 0; k < kStatSlots; ++k) {
+        s0 += v0[k];
+        s1 += v1[k];
+    }
+#pragma unroll
+    for (int k = 0; k < kStatSlots; ++k) {
+        sp[k * 2 * C] = 0.0;
+        sp[k * 2 * C + C] = 0.0;
+    }
+}
+
+// forward: s = sum x, q = sum x^2 over d.rows elements of channel c -> mean / invstd, running
+// stats and the affine coefficients scale = gamma*invstd, shift = beta - mean*scale.  The
+// per-channel inputs come in as values (g, b: gamma / beta or 1 / 0; rm, rv: the running stats,
+// used when run_mean is set) so that a caller can issue their loads together with the slot loads.
+__device__ __forceinline__ void bn_fin_fwd_channel(const BnFinDesc &d, int c, double s, double q, float g, float b,
+                                                   float rm, float rv) {
+    const int64_t rows = d.rows;
+    const double m = s / rows;
     double var = q / rows - m * m;
     if (var < 0) var = 0;
-    float is = rsqrtf(static_cast<float>(var) + eps);
-    mean[c] = static_cast<float>(m);
-    invstd[c] = is;
-    if (run_mean) {
-        double unbiased = rows > 1 ? var * rows / (rows - 1) : var;
-        run_mean[c] = (1.f - momentum) * run_mean[c] + momentum * static_cast<float>(m);
-        run_var[c] = (1.f - momentum) * run_var[c] + momentum * static_cast<float>(unbiased);
+    const float is = rsqrtf(static_cast<float>(var) + d.eps);
+    const float sc = g * is;
+    d.mean[c] = static_cast<float>(m);
+    d.invstd[c] = is;
+    if (d.run_mean) {
+        const double unbiased = rows > 1 ? var * rows / (rows - 1) : var;
+        d.run_mean[c] = (1.f - d.momentum) * rm + d.momentum * static_cast<float>(m);
+        d.run_var[c] = (1.f - d.momentum) * rv + d.momentum * static_cast<float>(unbiased);
     }
-    float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
-    float sc = g * is;
-    coef[c] = sc;
-    coef[C + c] = b - static_cast<float>(m) * sc;
+    d.coef[c] = sc;
+    d.coef[d.C + c] = b - static_cast<float>(m) * sc;
 }
 
-// Same outputs from f64 per-channel sums produced by a convolution epilogue
-// (conv.hip, EPI bit 0): kStatSlots slots of [sum x (C), sum x^2 (C)]; the sums are
-// re-zeroed for the next producer (self-cleaning workspace, no memset launch).
-__global__ __launch_bounds__(256) void bn_sums_finalize(double *__restrict__ sums, int C, int64_t rows,
-                                                        const float *__restrict__ gamma,
-                                                        const float *__restrict__ beta, float *mean, float *invstd,
-                                                        float *run_mean, float *run_var, float momentum, float eps,
-                                                        float *coef, int64_t *num_batches) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (num_batches && c == 0) num_batches[0] += 1;
-    if (c >= C) return;
-    // every input issued before any store: the slot sums and the channel's parameters / running
-    // stats (loaded behind the zeroing and output stores, each was a serial round trip: 5.7 us)
-    const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
-    const float rm = run_mean ? run_mean[c] : 0.f, rv = run_mean ? run_var[c] : 0.f;
-    const double *sp = sums + c;
-    double vs[kStatSlots], vq[kStatSlots];
-#pragma unroll
-    for (int k = 0; k < kStatSlots; ++k) {
-        vs[k] = sp[k * 2 * C];
-        vq[k] = sp[k * 2 * C + C];
-    }
-    double s = 0, q = 0;
-#pragma unroll
-    for (int k = 0; k < kStatSlots; ++k) {
-        s += vs[k];
-        q += vq[k];
-    }
-    double *zp = sums + c;
-#pragma unroll
-    for (int k = 0; k < kStatSlots; ++k) {
-        zp[k * 2 * C] = 0.0;
-        zp[k * 2 * C + C] = 0.0;
-    }
-    bn_fin_fwd_channel(c, C, s, q, rows, g, b, rm, rv, mean, invstd, run_mean, run_var, momentum, eps, coef);
+// Forward from the statistics pass's partials (folded parallel over chunks); num_batches_tracked is
+// bumped here instead of by a separate launch.
+__device__ __forceinline__ void bn_fin_fwd_partials(const BnFinDesc &d) {
+    const int c = blockIdx.x * kFoldCh + threadIdx.x % kFoldCh, kl = threadIdx.x / kFoldCh;
+    double sums[2];
+    fold_partials<2>(d.partial, d.nchunks, d.C, c, kl, sums);
+    if (d.nbt && blockIdx.x == 0 && threadIdx.x == 0) d.nbt[0] += 1;
+    if (kl != 0 || c >= d.C) return;
+    const float g = d.gamma ? d.gamma[c] : 1.f, b = d.beta ? d.beta[c] : 0.f;
+    const float rm = d.run_mean ? d.run_mean[c] : 0.f, rv = d.run_mean ? d.run_var[c] : 0.f;
+    bn_fin_fwd_channel(d, c, sums[0], sums[1], g, b, rm, rv);
 }
 
-// Several BNs' sums-finalizes in ONE launch (blockIdx.y = which BN): the deferred branch BNs of an
-// Inception block's concatenation are all finalized before any of their applies (ops/fused_bn.py
-// _BNConcatFn), 2-6 launches of ~5 us each that were back-to-back anyway.
-__global__ __launch_bounds__(256) void bn_sums_finalize_multi(BnFinBatch b) {
-    const BnFinDesc &d = b.d[blockIdx.y];
+// Forward from the f64 slot sums of a convolution epilogue (conv.hip, EPI bit 0).
+__device__ __forceinline__ void bn_fin_fwd_sums(const BnFinDesc &d) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (d.nbt && c == 0) d.nbt[0] += 1;
-    if (c >= d.C) return;
-    const int C = d.C;
-    const float g = d.gamma ? d.gamma[c] : 1.f, bb = d.beta ? d.beta[c] : 0.f;
+    if (c >= d.C) return;  // also a narrower BN of a batch
+    const float g = d.gamma ? d.gamma[c] : 1.f, b = d.beta ? d.beta[c] : 0.f;
     const float rm = d.run_mean ? d.run_mean[c] : 0.f, rv = d.run_mean ? d.run_var[c] : 0.f;
-    const double *sp = d.sums + c;
-    double vs[kStatSlots], vq[kStatSlots];
-#pragma unroll
-    for (int k = 0; k < kStatSlots; ++k) {
-        vs[k] = sp[k * 2 * C];
-        vq[k] = sp[k * 2 * C + C];
-    }
-    double s = 0, q = 0;
-#pragma unroll
-    for (int k = 0; k < kStatSlots; ++k) {
-        s += vs[k];
-        q += vq[k];
-    }
-    double *zp = d.sums + c;
-#pragma unroll
-    for (int k = 0; k < kStatSlots; ++k) {
-        zp[k * 2 * C] = 0.0;
-        zp[k * 2 * C + C] = 0.0;
-    }
-    bn_fin_fwd_channel(c, C, s, q, d.rows, g, bb, rm, rv, d.mean, d.invstd, d.run_mean, d.run_var, d.momentum, d.eps,
-                       d.coef);
+    double s, q;
+    fold_slots(d.sums, c, d.C, s, q);
+    bn_fin_fwd_channel(d, c, s, q, g, b, rm, rv);
 }
+
+// backward: s0 = sum dz, s1 = sum dz * x (dz = the gradient of the BN output under the ReLU gate);
+// g = gamma (or 1), mu / is = the forward batch mean / inverse std of channel c, as values.
+// dbeta = sum dz, dgamma = invstd * (sum dz*x - mean * sum dz); dx = k1*dz + k2*x + k3.
+__device__ __forceinline__ void bn_fin_bwd_channel(const BnBwdFinDesc &d, int c, double s0, double s1, float g,
+                                                   float mu, float is, bool training) {
+    const int C = d.C;
+    const double db = s0, dg = static_cast<double>(is) * (s1 - static_cast<double>(mu) * db);
+    d.dgamma[c] = static_cast<float>(dg);
+    d.dbeta[c] = static_cast<float>(db);
+    const float a = g * is;
+    if (training) {
+        const float inv_m = 1.f / static_cast<float>(d.rows);
+        const float k2 = -a * static_cast<float>(dg) * is * inv_m;
+        d.coef[c] = a;
+        d.coef[C + c] = k2;
+        d.coef[2 * C + c] = -a * static_cast<float>(db) * inv_m - k2 * mu;
+    } else {
+        d.coef[c] = a;
+        d.coef[C + c] = 0.f;
+        d.coef[2 * C + c] = 0.f;
+    }
+}
+
+// Backward from the reduce pass's partials.
+__device__ __forceinline__ void bn_fin_bwd_partials(const BnBwdFinDesc &d, bool training) {
+    if (static_cast<int>(blockIdx.x) * kFoldCh >= d.C) return;  // a narrower BN of a batch: uniform exit
+    const int c = blockIdx.x * kFoldCh + threadIdx.x % kFoldCh, kl = threadIdx.x / kFoldCh;
+    double sums[2];
+    fold_partials<2>(d.partial, d.nchunks, d.C, c, kl, sums);
+    if (kl != 0 || c >= d.C) return;
+    bn_fin_bwd_channel(d, c, sums[0], sums[1], d.gamma ? d.gamma[c] : 1.f, d.mean[c], d.invstd[c], training);
+}
+
+// Backward from the f64 slot sums of a data-gradient conv epilogue (conv.hip kEpiBwd*).
+__device__ __forceinline__ void bn_fin_bwd_sums(const BnBwdFinDesc &d) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= d.C) return;
+    const float g = d.gamma ? d.gamma[c] : 1.f, mu = d.mean[c], is = d.invstd[c];  // issued with the slot loads
+    double s0, s1;
+    fold_slots(d.sums, c, d.C, s0, s1);
+    bn_fin_bwd_channel(d, c, s0, s1, g, mu, is, d.training);
+}
+
+__global__ __launch_bounds__(kBlock) void bn_stats_finalize(BnFinDesc d) { bn_fin_fwd_partials(d); }
+__global__ __launch_bounds__(256) void bn_sums_finalize(BnFinDesc d) { bn_fin_fwd_sums(d); }
+// Several BNs' sums-finalizes in ONE launch: the deferred branch BNs of an Inception block's
+// concatenation are all finalized before any of their applies (ops/fused_bn.py _BNConcatFn), 2-6
+// launches of ~5 us each that were back-to-back anyway.
+__global__ __launch_bounds__(256) void bn_sums_finalize_multi(BnFinBatch b) { bn_fin_fwd_sums(b.d[blockIdx.y]); }
+
+__global__ __launch_bounds__(kBlock) void bn_bwd_finalize(BnBwdFinDesc d) { bn_fin_bwd_partials(d, d.training); }
+// Several training BNs' backward finalizes in ONE launch: the branch BNs of an Inception block's
+// concatenation (ops/fused_bn.py _BNConcatFn.backward).
+__global__ __launch_bounds__(kBlock) void bn_bwd_finalize_multi(BnBwdFinBatch b) {
+    bn_fin_bwd_partials(b.d[blockIdx.y], true);
+}
+__global__ __launch_bounds__(256) void bn_bwd_finalize_sums(BnBwdFinDesc d) { bn_fin_bwd_sums(d); }
 
 // Eval mode: coefficients from running stats.
 __global__ void bn_eval_coef(int C, const float *gamma, const float *beta, const float *run_mean,
@@ -529,7 +568,7 @@ __global__ __launch_bounds__(kBlock) void bn_pool_bwd_sums_kernel(const uint4 *_
 // ---------------------------------------------------------------- backward gradient sources
 
 // dy read directly ([rows, C]).
-// Two-phase interface so the reduce loop can put several rows of loads in
+// Two-step interface so the reduce loop can put several rows of loads in
 // flight before any arithmetic: fetch() issues the loads, get() unpacks.
 struct DirectGrad {
     const uint4 *dy;
@@ -707,87 +746,6 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_reduce_kernel(G grad, const uin
     reduce_to_partials<CVEC, 2>(acc, lds, partial, C, gridDim.x);
 }
 
-// dbeta = sum dz, dgamma = sum dz*xhat; dx = k1*dz + k2*x + k3.
-__global__ __launch_bounds__(kBlock) void bn_bwd_finalize(const float *partial, int nchunks, int C, int64_t rows,
-                                                          const float *gamma, const float *mean, const float *invstd,
-                                                          float *dgamma, float *dbeta, float *coef, bool training) {
-    const int c = blockIdx.x * kFoldCh + threadIdx.x % kFoldCh, kl = threadIdx.x / kFoldCh;
-    double sums[2];
-    fold_partials<2>(partial, nchunks, C, c, kl, sums);
-    if (kl != 0 || c >= C) return;
-    // sums[1] = sum(dz * x)  ->  dgamma = invstd * (sum(dz*x) - mean * sum(dz))
-    double db = sums[0], dg = static_cast<double>(invstd[c]) * (sums[1] - static_cast<double>(mean[c]) * db);
-    dgamma[c] = static_cast<float>(dg);
-    dbeta[c] = static_cast<float>(db);
-    float g = gamma ? gamma[c] : 1.f;
-    float a = g * invstd[c];
-    if (training) {
-        float inv_m = 1.f / static_cast<float>(rows);
-        float k2 = -a * static_cast<float>(dg) * invstd[c] * inv_m;
-        coef[c] = a;
-        coef[C + c] = k2;
-        coef[2 * C + c] = -a * static_cast<float>(db) * inv_m - k2 * mean[c];
-    } else {
-        coef[c] = a;
-        coef[C + c] = 0.f;
-        coef[2 * C + c] = 0.f;
-    }
-}
-
-// Several BNs' backward finalizes in ONE launch (blockIdx.y = which BN): the branch BNs of an
-// Inception block's concatenation (ops/fused_bn.py _BNConcatFn.backward).
-__global__ __launch_bounds__(kBlock) void bn_bwd_finalize_multi(BnBwdFinBatch b) {
-    const BnBwdFinDesc &d = b.d[blockIdx.y];
-    const int C = d.C;
-    if (static_cast<int>(blockIdx.x) * kFoldCh >= C) return;  // a narrower BN of the batch: uniform exit
-    const int c = blockIdx.x * kFoldCh + threadIdx.x % kFoldCh, kl = threadIdx.x / kFoldCh;
-    double sums[2];
-    fold_partials<2>(d.partial, d.nchunks, C, c, kl, sums);
-    if (kl != 0 || c >= C) return;
-    double db = sums[0], dg = static_cast<double>(d.invstd[c]) * (sums[1] - static_cast<double>(d.mean[c]) * db);
-    d.dgamma[c] = static_cast<float>(dg);
-    d.dbeta[c] = static_cast<float>(db);
-    float g = d.gamma ? d.gamma[c] : 1.f;
-    float a = g * d.invstd[c];
-    const float inv_m = 1.f / static_cast<float>(d.rows);
-    const float k2 = -a * static_cast<float>(dg) * d.invstd[c] * inv_m;
-    d.coef[c] = a;
-    d.coef[C + c] = k2;
-    d.coef[2 * C + c] = -a * static_cast<float>(db) * inv_m - k2 * d.mean[c];
-}
-
-// Same coefficients from the f64 slotted sums of a data-gradient conv epilogue
-// (conv.hip kEpiBwd*): sum dz, sum dz*x; the slots are re-zeroed.
-__global__ __launch_bounds__(256) void bn_bwd_finalize_sums(double *__restrict__ sums, int C, int64_t rows,
-                                                            const float *__restrict__ gamma,
-                                                            const float *__restrict__ mean,
-                                                            const float *__restrict__ invstd, float *dgamma,
-                                                            float *dbeta, float *coef, bool training) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    const float g = gamma ? gamma[c] : 1.f, mu = mean[c], is = invstd[c];  // issued with the slot loads
-    const double *sp = sums + c;
-    double v0[kStatSlots], v1[kStatSlots];
-#pragma unroll
-    for (int k = 0; k < kStatSlots; ++k) {
-        v0[k] = sp[k * 2 * C];
-        v1[k] = sp[k * 2 * C + C];
-    }
-    double s0 = 0, s1 = 0;
-#pragma unroll
-    for (int k = 0; k < kStatSlots; ++k) {
-        s0 += v0[k];
-        s1 += v1[k];
-    }
-    double *zp = sums + c;
-#pragma unroll
-    for (int k = 0; k < kStatSlots; ++k) {
-        zp[k * 2 * C] = 0.0;
-        zp[k * 2 * C + C] = 0.0;
-    }
-    bn_fin_bwd_channel(c, C, s0, s1, rows, g, mu, is, dgamma, dbeta, coef, training);
-}
-
 // ---------------------------------------------------------------- backward apply
 
 // DRES && dsx: the residual gradient also feeds a second BN (the downsample branch's, input dsx,
@@ -884,26 +842,28 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_apply_kernel(G grad, const uint
     }
 }
 
+// ---------------------------------------------------------------- launchers
+
+// The supported C / 8 values, once: dispatch_cvec and bn_supported_channels both come from this list.
+#define KF_BN_CVECS(X) X(4) X(6) X(8) X(10) X(12) X(16) X(20) X(24) X(32) X(40) X(48) X(56) X(64) X(128) X(256)
+
+// f(integral_constant<int, cvec>) for a supported cvec; false (and no call) for any other.
 template <typename F>
-void dispatch_cvec(int cvec, F &&f) {
+bool dispatch_cvec(int cvec, F &&f) {
     switch (cvec) {
-    case 4: f(std::integral_constant<int, 4>()); break;
-    case 6: f(std::integral_constant<int, 6>()); break;
-    case 10: f(std::integral_constant<int, 10>()); break;
-    case 12: f(std::integral_constant<int, 12>()); break;
-    case 20: f(std::integral_constant<int, 20>()); break;
-    case 24: f(std::integral_constant<int, 24>()); break;
-    case 40: f(std::integral_constant<int, 40>()); break;
-    case 48: f(std::integral_constant<int, 48>()); break;
-    case 56: f(std::integral_constant<int, 56>()); break;
-    case 8: f(std::integral_constant<int, 8>()); break;
-    case 16: f(std::integral_constant<int, 16>()); break;
-    case 32: f(std::integral_constant<int, 32>()); break;
-    case 64: f(std::integral_constant<int, 64>()); break;
-    case 128: f(std::integral_constant<int, 128>()); break;
-    case 256: f(std::integral_constant<int, 256>()); break;
-    default: break;
+#define KF_BN_CASE(N) \
+    case N: f(std::integral_constant<int, N>()); return true;
+        KF_BN_CVECS(KF_BN_CASE)
+#undef KF_BN_CASE
+    default: return false;
     }
+}
+
+template <typename F>
+void dispatch_relu_mode(int rm, F &&f) {
+    if (rm == RM_COEF) f(std::integral_constant<int, RM_COEF>());
+    else if (rm == RM_BITS) f(std::integral_constant<int, RM_BITS>());
+    else f(std::integral_constant<int, RM_NONE>());
 }
 
 // blocks of bn_threads<CVEC>() threads (a multiple of CVEC, so any grid keeps cv fixed)
@@ -915,89 +875,100 @@ int apply_grid(int64_t nvec, int cvec) {
     return static_cast<int>(g);
 }
 
-void launch_stats(const uint16_t *x, BNShape sh, const float *gamma, const float *beta, float *run_mean,
-                  float *run_var, float momentum, float eps, float *partial, float *mean, float *invstd, float *coef,
-                  int64_t *num_batches, hipStream_t s) {
-    const int C = sh.channels, cvec = C / 8;
-    Chunking ch = chunking(sh);
-    dispatch_cvec(cvec, [&](auto cvc) {
-        constexpr int CV = decltype(cvc)::value;
-        bn_stats_kernel<CV><<<ch.nchunks, bn_threads<CV>(), 0, s>>>(reinterpret_cast<const uint4 *>(x), sh.rows,
-                                                          ch.rows_per_chunk, partial);
+// Where the forward coefficients come from: the slot sums (unless the batched launch has already
+// finalized them), otherwise the statistics pass over x, otherwise (eval mode) the running stats.
+void launch_fwd_coef(BnFinDesc d, const uint16_t *x, bool training, bool prefinalized, hipStream_t s) {
+    const int C = d.C;
+    if (!training) {
+        bn_eval_coef<<<(C + 255) / 256, 256, 0, s>>>(C, d.gamma, d.beta, d.run_mean, d.run_var, d.eps, d.mean,
+                                                     d.invstd, d.coef);
+    } else if (d.sums) {
+        if (!prefinalized) bn_sums_finalize<<<(C + 255) / 256, 256, 0, s>>>(d);
+    } else {
+        const Chunking ch = chunking({d.rows, C});
+        d.nchunks = ch.nchunks;
+        dispatch_cvec(C / 8, [&](auto cvc) {
+            constexpr int CV = decltype(cvc)::value;
+            bn_stats_kernel<CV><<<ch.nchunks, bn_threads<CV>(), 0, s>>>(reinterpret_cast<const uint4 *>(x), d.rows,
+                                                                        ch.rows_per_chunk, d.partial);
+        });
+        bn_stats_finalize<<<(C + kFoldCh - 1) / kFoldCh, kBlock, 0, s>>>(d);
+    }
+}
+
+// The backward's three steps over the gradient source G: reduce (the statistics pass into
+// bn.partial), finalize (from bn.sums when given, else from bn.partial), apply.
+
+int relu_mode(const BnBackwardArgs &a) { return !a.relu ? RM_NONE : (a.mask ? RM_BITS : RM_COEF); }
+
+template <class G>
+void bwd_reduce(G grad, const BnBackwardArgs &a, hipStream_t s) {
+    const BnBwdFinDesc &d = a.bn;
+    const Chunking ch = chunking({d.rows, d.C});
+    dispatch_cvec(d.C / 8, [&](auto cvc) {
+        dispatch_relu_mode(relu_mode(a), [&](auto rmc) {
+            constexpr int CV = decltype(cvc)::value, RM = decltype(rmc)::value;
+            bn_bwd_reduce_kernel<CV, RM, G><<<ch.nchunks, bn_threads<CV>(), 0, s>>>(
+                grad, reinterpret_cast<const uint4 *>(a.x), a.fcoef, a.mask, d.rows, ch.rows_per_chunk, d.partial,
+                bn_nt_mode());
+        });
     });
-    bn_stats_finalize<<<(C + kFoldCh - 1) / kFoldCh, kBlock, 0, s>>>(partial, ch.nchunks, C, sh.rows, gamma, beta,
-                                                                     mean, invstd, run_mean, run_var, momentum, eps,
-                                                                     coef, num_batches);
+}
+
+void bwd_finalize(BnBwdFinDesc d, hipStream_t s) {
+    if (d.sums) {
+        bn_bwd_finalize_sums<<<(d.C + 255) / 256, 256, 0, s>>>(d);
+    } else {
+        d.nchunks = chunking({d.rows, d.C}).nchunks;
+        bn_bwd_finalize<<<(d.C + kFoldCh - 1) / kFoldCh, kBlock, 0, s>>>(d);
+    }
 }
 
 template <class G>
-void launch_backward_impl(G grad, const uint16_t *x, const float *fcoef, const uint8_t *mask, const float *mean,
-                          const float *invstd, const float *gamma, BNShape sh, int rm, bool training, float *partial,
-                          float *dgamma, float *dbeta, float *coef, uint16_t *dx, uint16_t *dres, hipStream_t s,
-                          double *sums = nullptr, const uint16_t *dres_x = nullptr, double *dres_sums = nullptr,
-                          int phase = 0) {
-    // phase 0: everything; 1: the reduce pass only (statistics path, no sums); 2: the apply pass only
-    // (coef already finalized -- bn_bwd_finalize_multi); 3: statistics + finalize, no apply (the
-    // caller consumes coef itself: the stem's fused weight gradient)
-    const int C = sh.channels, cvec = C / 8;
-    const int64_t nvec = sh.rows * cvec;
-    Chunking ch = chunking(sh);
-    const uint4 *xx = reinterpret_cast<const uint4 *>(x);
-    if (phase == 2) {
-    } else if (sums) {
-        bn_bwd_finalize_sums<<<(C + 255) / 256, 256, 0, s>>>(sums, C, sh.rows, gamma, mean, invstd, dgamma, dbeta,
-                                                             coef, training);
-    } else {
-    dispatch_cvec(cvec, [&](auto cvc) {
-        constexpr int CV = decltype(cvc)::value;
-        auto go = [&](auto rmc) {
-            constexpr int RM = decltype(rmc)::value;
-            bn_bwd_reduce_kernel<CV, RM, G>
-                <<<ch.nchunks, bn_threads<CV>(), 0, s>>>(grad, xx, fcoef, mask, sh.rows, ch.rows_per_chunk, partial,
-                                                          bn_nt_mode());
-        };
-        if (rm == RM_COEF) go(std::integral_constant<int, RM_COEF>());
-        else if (rm == RM_BITS) go(std::integral_constant<int, RM_BITS>());
-        else go(std::integral_constant<int, RM_NONE>());
-    });
-    if (phase == 1) return;
-    bn_bwd_finalize<<<(C + kFoldCh - 1) / kFoldCh, kBlock, 0, s>>>(partial, ch.nchunks, C, sh.rows, gamma, mean,
-                                                                   invstd, dgamma, dbeta, coef, training);
-    }
-    if (phase == 3) return;
+void bwd_apply(G grad, const BnBackwardArgs &a, hipStream_t s) {
+    const BnBwdFinDesc &d = a.bn;
+    const int cvec = d.C / 8;
+    const int64_t nvec = d.rows * cvec;
     const int g = apply_grid(nvec, cvec);
-    uint4 *o = reinterpret_cast<uint4 *>(dx), *r = reinterpret_cast<uint4 *>(dres);
     dispatch_cvec(cvec, [&](auto cvc) {
-        constexpr int CV = decltype(cvc)::value;
-        auto go = [&](auto rmc, auto drc) {
-            constexpr int RM = decltype(rmc)::value;
-            constexpr bool DR = decltype(drc)::value;
-            bn_bwd_apply_kernel<CV, RM, DR, G><<<g, bn_threads<CV>(), 0, s>>>(
-                grad, xx, fcoef, mask, coef, o, r, nvec, DR ? reinterpret_cast<const uint4 *>(dres_x) : nullptr,
-                DR ? dres_sums : nullptr, bn_nt_mode());
-        };
-        using T = std::true_type;
-        using F = std::false_type;
-        if (rm == RM_COEF) {
-            if (dres) go(std::integral_constant<int, RM_COEF>(), T());
-            else go(std::integral_constant<int, RM_COEF>(), F());
-        } else if (rm == RM_BITS) {
-            if (dres) go(std::integral_constant<int, RM_BITS>(), T());
-            else go(std::integral_constant<int, RM_BITS>(), F());
-        } else {
-            if (dres) go(std::integral_constant<int, RM_NONE>(), T());
-            else go(std::integral_constant<int, RM_NONE>(), F());
-        }
+        dispatch_relu_mode(relu_mode(a), [&](auto rmc) {
+            auto go = [&](auto drc) {
+                constexpr int CV = decltype(cvc)::value, RM = decltype(rmc)::value;
+                constexpr bool DR = decltype(drc)::value;
+                bn_bwd_apply_kernel<CV, RM, DR, G><<<g, bn_threads<CV>(), 0, s>>>(
+                    grad, reinterpret_cast<const uint4 *>(a.x), a.fcoef, a.mask, d.coef,
+                    reinterpret_cast<uint4 *>(a.dx), reinterpret_cast<uint4 *>(a.dres), nvec,
+                    DR ? reinterpret_cast<const uint4 *>(a.dres_x) : nullptr, DR ? a.dres_sums : nullptr, bn_nt_mode());
+            };
+            if (a.dres) go(std::true_type());
+            else go(std::false_type());
+        });
     });
+}
+
+// f(the gradient source of a.dy): read directly, or as a channel slice of a wider tensor.
+template <typename F>
+void with_grad(const BnBackwardArgs &a, F &&f) {
+    const uint4 *dy = reinterpret_cast<const uint4 *>(a.dy);
+    if (a.dy_ld > 0 && a.dy_ld != a.bn.C) {
+        if (a.dy_ld % 8) throw std::invalid_argument("bn_backward: dy row stride must be a multiple of 8");
+        f(StridedGrad{dy, a.dy_ld / 8});
+    } else {
+        f(DirectGrad{dy, (bn_nt_mode() & 1) != 0});
+    }
 }
 
 }  // namespace
 
-void launch_bn_bwd_finalize_multi(const BnBwdFinBatch &b, hipStream_t s) {
+void launch_bn_bwd_finalize_multi(BnBwdFinBatch b, hipStream_t s) {
     if (b.n <= 0) return;
     if (b.n > kBnFinMax) throw std::invalid_argument("bn_bwd_finalize_multi: too many BNs");
     int cmax = 0;
-    for (int i = 0; i < b.n; ++i) cmax = b.d[i].C > cmax ? b.d[i].C : cmax;
+    for (int i = 0; i < b.n; ++i) {
+        BnBwdFinDesc &d = b.d[i];
+        d.nchunks = chunking({d.rows, d.C}).nchunks;
+        cmax = d.C > cmax ? d.C : cmax;
+    }
     bn_bwd_finalize_multi<<<dim3((cmax + kFoldCh - 1) / kFoldCh, b.n), kBlock, 0, s>>>(b);
 }
 
@@ -1010,50 +981,34 @@ void launch_bn_sums_finalize_multi(const BnFinBatch &b, hipStream_t s) {
 }
 
 bool bn_supported_channels(int C) {
-    if (C % 8) return false;
-    switch (C / 8) {
-    case 4: case 6: case 8: case 10: case 12: case 16: case 20: case 24: case 32: case 40: case 48: case 56:
-    case 64: case 128: case 256:
-        return true;
-    default:
-        return false;
-    }
+    return C % 8 == 0 && dispatch_cvec(C / 8, [](auto) {});
 }
 
 int bn_num_chunks(BNShape sh) { return chunking(sh).nchunks; }
 
-void launch_bn_forward(const uint16_t *x, const uint16_t *res, const float *gamma, const float *beta, uint16_t *y,
-                       uint8_t *mask, BNShape sh, bool relu, bool training, float *run_mean, float *run_var,
-                       float momentum, float eps, float *partial, float *mean, float *invstd, float *coef,
-                       int64_t *num_batches, hipStream_t s, double *sums, const float *res_coef, bool apply,
-                       int64_t y_ld, bool prefinalized) {
-    const int C = sh.channels, cvec = C / 8;
-    if (y_ld > 0 && (y_ld % 8 || y_ld < C || res || !relu))
+void launch_bn_forward(const BnForwardArgs &a, hipStream_t s) {
+    const int C = a.bn.C, cvec = C / 8;
+    const int64_t y_ld = a.y_ld;
+    if (y_ld > 0 && (y_ld % 8 || y_ld < C || a.res || !a.relu))
         throw std::invalid_argument("bn_forward: a strided output needs BN+ReLU without residual, row stride % 8");
-    const int64_t nvec = sh.rows * cvec;
-    if (training && sums) {
-        if (!prefinalized)
-            bn_sums_finalize<<<(C + 255) / 256, 256, 0, s>>>(sums, C, sh.rows, gamma, beta, mean, invstd, run_mean,
-                                                             run_var, momentum, eps, coef, num_batches);
-    } else if (training) {
-        launch_stats(x, sh, gamma, beta, run_mean, run_var, momentum, eps, partial, mean, invstd, coef, num_batches,
-                     s);
-    } else {
-        bn_eval_coef<<<(C + 255) / 256, 256, 0, s>>>(C, gamma, beta, run_mean, run_var, eps, mean, invstd, coef);
-    }
-    if (!apply) return;
+    launch_fwd_coef(a.bn, a.x, a.training, a.prefinalized, s);
+    if (!a.apply) return;
+    const int64_t nvec = a.bn.rows * cvec;
     const int g = apply_grid(nvec, cvec);
+    const bool relu = a.relu;
     const int ntm = bn_nt_mode();
+    const float *coef = a.bn.coef;
+    uint8_t *mask = a.mask;
     dispatch_cvec(cvec, [&](auto cvc) {
         constexpr int CV = decltype(cvc)::value;
         constexpr int NT = bn_threads<CV>();
-        const uint4 *xv = reinterpret_cast<const uint4 *>(x);
-        const uint4 *rv = reinterpret_cast<const uint4 *>(res);
-        uint4 *yv = reinterpret_cast<uint4 *>(y);
-        if (res && res_coef) {
-            if (relu) bn_apply_kernel<CV, true, true, true><<<g, NT, 0, s>>>(xv, rv, coef, yv, mask, nvec, res_coef, ntm);
-            else bn_apply_kernel<CV, true, false, true><<<g, NT, 0, s>>>(xv, rv, coef, yv, mask, nvec, res_coef, ntm);
-        } else if (res) {
+        const uint4 *xv = reinterpret_cast<const uint4 *>(a.x);
+        const uint4 *rv = reinterpret_cast<const uint4 *>(a.res);
+        uint4 *yv = reinterpret_cast<uint4 *>(a.y);
+        if (a.res && a.res_coef) {
+            if (relu) bn_apply_kernel<CV, true, true, true><<<g, NT, 0, s>>>(xv, rv, coef, yv, mask, nvec, a.res_coef, ntm);
+            else bn_apply_kernel<CV, true, false, true><<<g, NT, 0, s>>>(xv, rv, coef, yv, mask, nvec, a.res_coef, ntm);
+        } else if (a.res) {
             if (relu) bn_apply_kernel<CV, true, true><<<g, NT, 0, s>>>(xv, rv, coef, yv, mask, nvec, nullptr, ntm);
             else bn_apply_kernel<CV, true, false><<<g, NT, 0, s>>>(xv, rv, coef, yv, mask, nvec, nullptr, ntm);
         } else if (y_ld > 0 && y_ld != C) {
@@ -1066,21 +1021,18 @@ void launch_bn_forward(const uint16_t *x, const uint16_t *res, const float *gamm
     });
 }
 
-void launch_bn_backward(const uint16_t *dy, const uint16_t *x, const float *fcoef, const uint8_t *mask,
-                        const float *mean, const float *invstd, const float *gamma, BNShape sh, bool relu,
-                        bool training, float *partial, float *dgamma, float *dbeta, float *coef, uint16_t *dx,
-                        uint16_t *dres, hipStream_t s, double *sums, const uint16_t *dres_x, double *dres_sums,
-                        int64_t dy_ld, int phase) {
-    const int rm = !relu ? RM_NONE : (mask ? RM_BITS : RM_COEF);
-    if (dy_ld > 0 && dy_ld != sh.channels) {
-        if (dy_ld % 8) throw std::invalid_argument("bn_backward: dy row stride must be a multiple of 8");
-        launch_backward_impl(StridedGrad{reinterpret_cast<const uint4 *>(dy), dy_ld / 8}, x, fcoef, mask, mean, invstd,
-                             gamma, sh, rm, training, partial, dgamma, dbeta, coef, dx, dres, s, sums, dres_x,
-                             dres_sums, phase);
-        return;
-    }
-    launch_backward_impl(DirectGrad{reinterpret_cast<const uint4 *>(dy), (bn_nt_mode() & 1) != 0}, x, fcoef, mask, mean, invstd, gamma, sh, rm,
-                         training, partial, dgamma, dbeta, coef, dx, dres, s, sums, dres_x, dres_sums, phase);
+void launch_bn_backward_reduce(const BnBackwardArgs &a, hipStream_t s) {
+    with_grad(a, [&](auto grad) { bwd_reduce(grad, a, s); });
+}
+
+void launch_bn_backward_apply(const BnBackwardArgs &a, hipStream_t s) {
+    with_grad(a, [&](auto grad) { bwd_apply(grad, a, s); });
+}
+
+void launch_bn_backward(const BnBackwardArgs &a, hipStream_t s) {
+    if (!a.bn.sums) launch_bn_backward_reduce(a, s);
+    bwd_finalize(a.bn, s);
+    launch_bn_backward_apply(a, s);
 }
 
 bool bn_pool_supported(BNShape sh, int H, int W) {
@@ -1088,56 +1040,46 @@ bool bn_pool_supported(BNShape sh, int H, int W) {
            sh.rows * (sh.channels / 8) < (int64_t(1) << 31);  // PoolGrad uses 32-bit index math
 }
 
-void launch_bn_pool_forward(const uint16_t *x, const float *gamma, const float *beta, uint16_t *yp, uint8_t *arg,
-                            BNShape sh, int H, int W, bool training, float *run_mean, float *run_var, float momentum,
-                            float eps, float *partial, float *mean, float *invstd, float *coef, int64_t *num_batches,
-                            hipStream_t s, double *sums, uint16_t *xarg) {
-    const int C = sh.channels, cvec = C / 8;
-    if (training && sums) {
-        bn_sums_finalize<<<(C + 255) / 256, 256, 0, s>>>(sums, C, sh.rows, gamma, beta, mean, invstd, run_mean,
-                                                         run_var, momentum, eps, coef, num_batches);
-    } else if (training) {
-        launch_stats(x, sh, gamma, beta, run_mean, run_var, momentum, eps, partial, mean, invstd, coef, num_batches,
-                     s);
-    } else {
-        bn_eval_coef<<<(C + 255) / 256, 256, 0, s>>>(C, gamma, beta, run_mean, run_var, eps, mean, invstd, coef);
-    }
+void launch_bn_pool_forward(const BnPoolForwardArgs &a, hipStream_t s) {
+    const int cvec = a.bn.C / 8, H = a.H, W = a.W;
+    launch_fwd_coef(a.bn, a.x, a.training, false, s);
     const int OH = pool_out(H), OW = pool_out(W);
-    const int64_t N = sh.rows / (static_cast<int64_t>(H) * W);
+    const int64_t N = a.bn.rows / (static_cast<int64_t>(H) * W);
     const int64_t nout = N * OH * OW * cvec;
     const int g = apply_grid(nout, cvec);
     dispatch_cvec(cvec, [&](auto cvc) {
         constexpr int CV = decltype(cvc)::value;
-        bn_pool_apply_kernel<CV><<<g, bn_threads<CV>(), 0, s>>>(reinterpret_cast<const uint4 *>(x), coef,
-                                                      reinterpret_cast<uint4 *>(yp), reinterpret_cast<uint2 *>(arg), H,
-                                                      W, OH, OW, nout, reinterpret_cast<uint4 *>(xarg));
+        bn_pool_apply_kernel<CV><<<g, bn_threads<CV>(), 0, s>>>(
+            reinterpret_cast<const uint4 *>(a.x), a.bn.coef, reinterpret_cast<uint4 *>(a.yp),
+            reinterpret_cast<uint2 *>(a.arg), H, W, OH, OW, nout, reinterpret_cast<uint4 *>(a.xarg));
     });
 }
 
-void launch_bn_pool_backward(const uint16_t *dyp, const uint8_t *arg, const uint16_t *x, const float *fcoef,
-                             const float *mean, const float *invstd, const float *gamma, BNShape sh, int H, int W,
-                             bool training, float *partial, float *dgamma, float *dbeta, float *coef, uint16_t *dx,
-                             hipStream_t s, const uint16_t *xarg, double *sums, bool apply) {
-    if (xarg && sums && training) {
-        const int C = sh.channels, cvec = C / 8;
-        const int64_t nvec = sh.rows / (static_cast<int64_t>(H) * W) * pool_out(H) * pool_out(W) * cvec;
+void launch_bn_pool_backward(const BnPoolBackwardArgs &p, hipStream_t s) {
+    const int H = p.H, W = p.W;
+    BnBackwardArgs a;  // BN + ReLU gated by the forward coefficients, the gradient gathered through PoolGrad
+    a.bn = p.bn, a.x = p.x, a.relu = true, a.fcoef = p.fcoef, a.dx = p.dx;
+    const uint4 *dyp = reinterpret_cast<const uint4 *>(p.dyp);
+    if (p.xarg && a.bn.sums && a.bn.training) {
+        const int cvec = a.bn.C / 8;
+        const int64_t nvec = a.bn.rows / (static_cast<int64_t>(H) * W) * pool_out(H) * pool_out(W) * cvec;
         const int g = apply_grid(nvec, cvec);
         dispatch_cvec(cvec, [&](auto cvc) {
             constexpr int CV = decltype(cvc)::value;
-            bn_pool_bwd_sums_kernel<CV><<<g, bn_threads<CV>(), 0, s>>>(
-                reinterpret_cast<const uint4 *>(dyp), reinterpret_cast<const uint4 *>(xarg), fcoef, sums, nvec);
+            bn_pool_bwd_sums_kernel<CV><<<g, bn_threads<CV>(), 0, s>>>(dyp, reinterpret_cast<const uint4 *>(p.xarg),
+                                                                       p.fcoef, a.bn.sums, nvec);
         });
     } else {
-        sums = nullptr;
+        a.bn.sums = nullptr;
     }
     const uint64_t m_hw = (uint64_t(1) << 40) / (static_cast<uint64_t>(H) * W) + 1;
     const uint64_t m_w = (uint64_t(1) << 40) / static_cast<uint64_t>(W) + 1;
-    if (static_cast<uint64_t>(sh.rows) * H * W >= (uint64_t(1) << 40))
+    if (static_cast<uint64_t>(a.bn.rows) * H * W >= (uint64_t(1) << 40))
         throw std::invalid_argument("bn_pool_backward: too many rows for the 40-bit division");
-    PoolGrad pg{reinterpret_cast<const uint4 *>(dyp), reinterpret_cast<const uint2 *>(arg), H, W, pool_out(H),
-                pool_out(W), m_hw, m_w};
-    launch_backward_impl(pg, x, fcoef, nullptr, mean, invstd, gamma, sh, RM_COEF, training, partial, dgamma, dbeta,
-                         coef, dx, nullptr, s, sums, nullptr, nullptr, apply ? 0 : 3);
+    PoolGrad pg{dyp, reinterpret_cast<const uint2 *>(p.arg), H, W, pool_out(H), pool_out(W), m_hw, m_w};
+    if (!a.bn.sums) bwd_reduce(pg, a, s);
+    bwd_finalize(a.bn, s);
+    if (p.apply) bwd_apply(pg, a, s);
 }
 
 }  // namespace kfk

@@ -313,78 +313,118 @@ struct BNShape {
 };
 bool bn_supported_channels(int C);
 int bn_num_chunks(BNShape sh);  // partial scratch = 2 * nchunks * C floats
-// Training: batch stats -> mean/invstd, running stats update, coef = [scale; shift]
-// (2C floats), y = act(x*scale + shift [+ res]).  Eval: running stats.
-// With res && relu, mask (rows*C/8 bytes) receives the ReLU bits for the backward.
-// num_batches (optional, int64 on device) is incremented in training mode.
-// Batched sums-finalize of up to kBnFinMax BNs (the f64 slotted sums of their producing convs): mean,
-// invstd, running stats, coef = [scale; shift], num_batches += 1, slots re-zeroed -- one launch.
+
+// One BN's forward finalize: batch sums -> mean / invstd, running stats update, coef.  Also the
+// BN-describing part of the forward launchers' arguments (eval mode reads gamma, beta, the running
+// stats and eps, and writes mean / invstd / coef from them).
 struct BnFinDesc {
-    double *sums;
-    const float *gamma, *beta;
-    float *mean, *invstd, *run_mean, *run_var, *coef;
-    int64_t *nbt;
-    int64_t rows;
-    int C;
-    float momentum, eps;
+    int64_t rows = 0;  // N*H*W
+    int C = 0;
+    const float *gamma = nullptr, *beta = nullptr;  // f32 [C]; nullptr: 1 / 0
+    float *run_mean = nullptr, *run_var = nullptr;  // f32 [C], optional in training mode: momentum update
+    int64_t *nbt = nullptr;  // num_batches_tracked (optional, int64 on device): += 1 in training mode
+    float momentum = 0.f, eps = 0.f;
+    float *mean = nullptr, *invstd = nullptr;  // out, f32 [C]
+    float *coef = nullptr;                     // out, f32 [scale; shift] (2C): y = x*scale + shift
+    double *sums = nullptr;    // f64 kStatSlots x [sum x; sum x^2] from a conv epilogue -> no statistics pass; re-zeroed
+    float *partial = nullptr;  // scratch of the statistics pass (training without sums): 2 * bn_num_chunks * C floats
+    int nchunks = 0;           // chunks of `partial`; set by the launcher
 };
 constexpr int kBnFinMax = 8;
 struct BnFinBatch {
     BnFinDesc d[kBnFinMax];
     int n;
 };
+// Batched sums-finalize of up to kBnFinMax training BNs (every d.sums set) -- one launch.
 void launch_bn_sums_finalize_multi(const BnFinBatch &b, hipStream_t s);
-// Batched backward finalize (statistics path: the reduce pass's partials) of up to kBnFinMax training BNs.
+
+// One BN's backward finalize: sum dz, sum dz*x -> dgamma / dbeta and the backward-apply coefficients.
 struct BnBwdFinDesc {
-    const float *partial;
-    int nchunks, C;
-    int64_t rows;
-    const float *gamma, *mean, *invstd;
-    float *dgamma, *dbeta, *coef;
+    int64_t rows = 0;  // N*H*W
+    int C = 0;
+    const float *gamma = nullptr;                    // f32 [C]; nullptr: 1
+    const float *mean = nullptr, *invstd = nullptr;  // the forward's, f32 [C]
+    float *dgamma = nullptr, *dbeta = nullptr;       // out, f32 [C]
+    float *coef = nullptr;     // out / scratch, f32 [k1; k2; k3] (3C): dx = k1*dz + k2*x + k3
+    bool training = true;      // false: k2 = k3 = 0 (the batch statistics do not depend on x)
+    double *sums = nullptr;    // f64 kStatSlots x [sum dz; sum dz*x] from a conv epilogue -> no reduce pass; re-zeroed
+    float *partial = nullptr;  // scratch of the reduce pass (no sums): 2 * bn_num_chunks * C floats
+    int nchunks = 0;           // chunks of `partial`; set by the launcher
 };
 struct BnBwdFinBatch {
     BnBwdFinDesc d[kBnFinMax];
     int n;
 };
-void launch_bn_bwd_finalize_multi(const BnBwdFinBatch &b, hipStream_t s);
+// Batched backward finalize (from the reduce passes' partials) of up to kBnFinMax training BNs -- one launch.
+void launch_bn_bwd_finalize_multi(BnBwdFinBatch b, hipStream_t s);
 
-void launch_bn_forward(const uint16_t *x, const uint16_t *res, const float *gamma, const float *beta, uint16_t *y,
-                       uint8_t *mask, BNShape sh, bool relu, bool training, float *run_mean, float *run_var,
-                       float momentum, float eps, float *partial, float *mean, float *invstd, float *coef,
-                       int64_t *num_batches, hipStream_t s, double *sums = nullptr, const float *res_coef = nullptr,
-                       bool apply = true, int64_t y_ld = 0, bool prefinalized = false);
-// (prefinalized: mean / invstd / coef were already written from `sums` by the batched
-// bn_finalize_multi launch -- no finalize launch here.
-// (y_ld > 0: y is a channel slice of a wider NHWC tensor with that row stride (elements); BN+ReLU only.
-// (sums: f64 [2C] batch sums from a conv epilogue -> no statistics pass; re-zeroed.
-//  res_coef: the residual is res*res_coef[c] + res_coef[C+c] (another BN's input and
-//  coefficients); apply = false: statistics / coefficients only, y untouched.)
-// dz = dy * relu'(.)  -- from mask bits if given, else recomputed as x*fcoef[0:C] + fcoef[C:2C] > 0
-// (fcoef = the forward's coef) ; dgamma/dbeta (f32) ; dx = k1*dz + k2*x + k3 ; dres = dz.
-// coef scratch: 3C floats.
-void launch_bn_backward(const uint16_t *dy, const uint16_t *x, const float *fcoef, const uint8_t *mask,
-                        const float *mean, const float *invstd, const float *gamma, BNShape sh, bool relu,
-                        bool training, float *partial, float *dgamma, float *dbeta, float *coef, uint16_t *dx,
-                        uint16_t *dres, hipStream_t s, double *sums = nullptr, const uint16_t *dres_x = nullptr,
-                        double *dres_sums = nullptr, int64_t dy_ld = 0, int phase = 0);
-// (dres_x / dres_sums: dres also feeds a second, ReLU-free BN with input dres_x -- its backward
-//  sums go to dres_sums, zeroed f64 [slots][2][C])
-// (sums: f64 kStatSlots x [sum dz; sum dz*x] from a conv epilogue -> no reduce pass; re-zeroed.)
+// Training: batch stats -> mean/invstd, running stats update, coef = [scale; shift]
+// (2C floats), y = act(x*scale + shift [+ res]).  Eval: running stats.
+struct BnForwardArgs {
+    BnFinDesc bn;
+    const uint16_t *x = nullptr;
+    bool training = true;
+    bool prefinalized = false;  // mean / invstd / coef were already written from bn.sums by the batched
+                                // bn_finalize_multi launch -- no finalize launch here
+    bool apply = true;          // false: statistics / coefficients only, y untouched
+    bool relu = false;
+    const uint16_t *res = nullptr;
+    const float *res_coef = nullptr;  // the residual is res*res_coef[c] + res_coef[C+c] (another BN's input and coefficients)
+    uint16_t *y = nullptr;
+    int64_t y_ld = 0;         // > 0: y is a channel slice of a wider NHWC tensor with that row stride (elements); BN+ReLU only
+    uint8_t *mask = nullptr;  // with res && relu: rows*C/8 bytes, receives the ReLU bits for the backward
+};
+void launch_bn_forward(const BnForwardArgs &a, hipStream_t s);
+
+// dz = dy * relu'(.) ; dgamma/dbeta (f32) ; dx = k1*dz + k2*x + k3 ; dres = dz.
+struct BnBackwardArgs {
+    BnBwdFinDesc bn;
+    const uint16_t *dy = nullptr, *x = nullptr;
+    int64_t dy_ld = 0;  // > 0: dy is a channel slice of a wider NHWC tensor with that row stride (elements)
+    bool relu = false;
+    const float *fcoef = nullptr;   // the forward's coef: without mask, relu' is recomputed as x*fcoef[0:C] + fcoef[C:2C] > 0
+    const uint8_t *mask = nullptr;  // the forward's ReLU bits, if it wrote them
+    uint16_t *dx = nullptr;
+    uint16_t *dres = nullptr;  // optional
+    // dres also feeds a second, ReLU-free BN with input dres_x -- its backward sums go to dres_sums,
+    // zeroed f64 [slots][2][C]
+    const uint16_t *dres_x = nullptr;
+    double *dres_sums = nullptr;
+};
+// reduce (the statistics pass into bn.partial; skipped with bn.sums), finalize, apply.
+void launch_bn_backward(const BnBackwardArgs &a, hipStream_t s);
+// The reduce and the apply step alone, for a caller that finalizes several BNs between them in one
+// launch (launch_bn_bwd_finalize_multi).
+void launch_bn_backward_reduce(const BnBackwardArgs &a, hipStream_t s);
+void launch_bn_backward_apply(const BnBackwardArgs &a, hipStream_t s);
 
 // ResNet stem: y = maxpool3x3s2p1(relu(bn(x))), x = [N, H, W, C] (rows = N*H*W).
-// arg receives the window argmax (0..8) per pooled element (bytes).
 inline int pool_out(int h) { return (h + 2 - 3) / 2 + 1; }
 bool bn_pool_supported(BNShape sh, int H, int W);
-void launch_bn_pool_forward(const uint16_t *x, const float *gamma, const float *beta, uint16_t *yp, uint8_t *arg,
-                            BNShape sh, int H, int W, bool training, float *run_mean, float *run_var, float momentum,
-                            float eps, float *partial, float *mean, float *invstd, float *coef, int64_t *num_batches,
-                            hipStream_t s, double *sums = nullptr, uint16_t *xarg = nullptr);
-// xarg + sums (zeroed f64 [slots][2][C]): the BN sums come from the pooled map (exact identity,
-// see bn_pool_bwd_sums_kernel) instead of the full-resolution reduce pass.
-void launch_bn_pool_backward(const uint16_t *dyp, const uint8_t *arg, const uint16_t *x, const float *fcoef,
-                             const float *mean, const float *invstd, const float *gamma, BNShape sh, int H, int W,
-                             bool training, float *partial, float *dgamma, float *dbeta, float *coef, uint16_t *dx,
-                             hipStream_t s, const uint16_t *xarg = nullptr, double *sums = nullptr, bool apply = true);
+struct BnPoolForwardArgs {
+    BnFinDesc bn;
+    const uint16_t *x = nullptr;
+    int H = 0, W = 0;
+    bool training = true;
+    uint16_t *yp = nullptr;    // [N, OH, OW, C]
+    uint8_t *arg = nullptr;    // the window argmax (0..8) per pooled element (bytes)
+    uint16_t *xarg = nullptr;  // optional: x at each window's argmax, for the backward's pooled sums
+};
+void launch_bn_pool_forward(const BnPoolForwardArgs &a, hipStream_t s);
+struct BnPoolBackwardArgs {
+    BnBwdFinDesc bn;  // bn.partial always; bn.sums: see xarg
+    const uint16_t *dyp = nullptr;  // [N, OH, OW, C]
+    const uint8_t *arg = nullptr;
+    const uint16_t *x = nullptr;
+    const float *fcoef = nullptr;
+    int H = 0, W = 0;
+    // xarg + bn.sums (zeroed f64 [slots][2][C]): the BN sums come from the pooled map (exact identity,
+    // see bn_pool_bwd_sums_kernel) instead of the full-resolution reduce pass.
+    const uint16_t *xarg = nullptr;
+    bool apply = true;  // false: reduce + finalize only, the caller consumes bn.coef itself (stem_wgrad_bnp)
+    uint16_t *dx = nullptr;
+};
+void launch_bn_pool_backward(const BnPoolBackwardArgs &a, hipStream_t s);
 
 // Conv bias (+ ReLU) on NHWC bf16 [rows, C] (bias_act.hip): forward in place; backward
 // dz = dy * (y > 0) (relu) and dbias[c] = sum over rows (f32, deterministic: per-block partials

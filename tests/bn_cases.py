@@ -74,6 +74,10 @@ UNIT_SHAPES = CHANNEL_SHAPES + SMALL_SHAPES + RAGGED_SHAPES
 POOL_SHAPES = [(2, 64, 2, 2), (3, 32, 3, 2), (2, 64, 15, 17), (3, 128, 8, 8)]
 MULTI_FWD = [(3, 48, 5, 7), (3, 192, 5, 7), (3, 320, 5, 7)]   # bn_finalize_multi: three BNs of different C
 MULTI_BWD = [(3, 48, 5, 7), (3, 192, 5, 7), (3, 32, 5, 7)]    # bn_backward_multi: two narrower than the widest
+# A full batch of kBnFinMax = 8 descriptors as (shape, rep): the shapes above repeated, every repeat with seeds
+# of its own (rep > 0); the last BN of each batch is narrower than the widest.
+MULTI8_FWD = [(s, i // 3) for i, s in enumerate((MULTI_FWD * 3)[:8])]
+MULTI8_BWD = [(s, i // 3) for i, s in enumerate((MULTI_BWD[1:] + MULTI_BWD[:1]) * 3)][:8]
 
 
 def seed_of(*key) -> int:
@@ -89,23 +93,26 @@ def _ch(t):
     return t.double().view(1, -1, 1, 1)
 
 
-def _ints(shape, dense, name, hi, off):
+def _ints(shape, dense, name, hi, off, rep=0):
+    seed = seed_of(name, shape, rep) if rep else seed_of(name, shape)
     if dense:
-        return integer_data(shape, "dense", seed_of(name, shape))
-    return integer_data(shape, "ties", seed_of(name, shape), hi=hi) - off
+        return integer_data(shape, "dense", seed)
+    return integer_data(shape, "ties", seed, hi=hi) - off
 
 
-def make_case(shape):
-    """The CPU float32 inputs of one shape (NCHW; the GPU tests cast x / dy / res to bf16 channels_last).
+def make_case(shape, rep=0):
+    """The CPU float32 inputs of one shape (NCHW; the GPU tests cast x / dy / res to bf16 channels_last);
+    ``rep`` > 0: another draw of the same recipe (the repeated shapes of MULTI8_*).
     Cached, except for the two large shapes (0.2 GB each), which one test builds and drops."""
-    return _build_case(shape) if shape in LARGE_SHAPES else _cached_case(shape)
+    return _build_case(shape, rep) if shape in LARGE_SHAPES else _cached_case(shape, rep)
 
 
-def _build_case(shape):
+def _build_case(shape, rep=0):
     N, C, H, W = shape
     dense = shape in LARGE_SHAPES
-    g = torch.Generator().manual_seed(seed_of("params", shape, SALT.get(shape, 0)))
-    x = _ints(shape, dense, "x", 16, 7)
+    salt = SALT.get((shape, rep) if rep else shape, 0)
+    g = torch.Generator().manual_seed(seed_of("params", shape, salt, rep) if rep else seed_of("params", shape, salt))
+    x = _ints(shape, dense, "x", 16, 7, rep)
     x[:, CONST_CH] = 1.0
     x[:, NEAR_CH] = 1.0
     x[N - 1, NEAR_CH, H - 1, W - 1] = 2.0
@@ -116,8 +123,8 @@ def _build_case(shape):
         gamma *= GAMMA_SINGLE_ROW
     beta = torch.randn(C, generator=g) * 0.5
     beta[CONST_CH] = CONST_BETA
-    c = {"shape": shape, "rows": rows_of(shape), "x": x, "dy": _ints(shape, dense, "dy", 8, 3),
-         "res": _ints(shape, dense, "res", 8, 4), "dsx": _ints(shape, dense, "dsx", 8, 3),
+    c = {"shape": shape, "rows": rows_of(shape), "x": x, "dy": _ints(shape, dense, "dy", 8, 3, rep),
+         "res": _ints(shape, dense, "res", 8, 4, rep), "dsx": _ints(shape, dense, "dsx", 8, 3, rep),
          "gamma": gamma, "beta": beta,
          "rm": torch.randn(C, generator=g) * 0.3, "rv": torch.rand(C, generator=g) + 0.5}
     # statistics the backward tests supply themselves (general f32 values, not the batch statistics of x)

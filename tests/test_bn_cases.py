@@ -153,6 +153,16 @@ def test_emulation_passes_every_assertion(shape):
     assert n + 1 == 12
 
 
+@pytest.mark.parametrize("shape,rep", sorted(set(B.MULTI8_FWD + B.MULTI8_BWD)), ids=str)
+def test_recipes_of_the_full_batches(shape, rep):
+    """The recipes of the eight-BN batches (the repeats are draws of their own): the preconditions, and the
+    emulation through the assertions their GPU tests apply, with the ambiguous-share cap."""
+    c = B.make_case(shape, rep)
+    B.check_case(c)
+    _check_fwd(c, B.emu_forward(c, True, stats_of=c["dsx"]), True, False, False, c["dsx"])
+    _check_bwd(c, B.emu_backward(c, True), True, True, False)
+
+
 @pytest.mark.parametrize("shape", B.POOL_SHAPES, ids=str)
 def test_pool_emulation_passes_and_its_mutants_fail(shape):
     """The stem pool's assertions on an f32 emulation: the clean one passes (forward, and the backward of the

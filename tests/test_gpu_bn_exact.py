@@ -1,4 +1,4 @@
-"""Element-wise float64 tests of the fused BatchNorm kernels (csrc/kernels/bn.hip, bn_fin.hpp): forward
+"""Element-wise float64 tests of the fused BatchNorm kernels (csrc/kernels/bn.hip): forward
 statistics, finalize (single, from f64 slot sums, batched), apply, backward reduce / finalize / apply and
 the stem's BN + ReLU + MaxPool, at every supported channel count and at the shapes where the launchers take
 another path (rows < RPI, one row, ragged chunks, the chunk cap, the grid cap).
@@ -37,9 +37,9 @@ def _dev(t):
 class Case:
     """A bn_cases recipe on the GPU: f32 NCHW tensors for the references, bf16 channels_last for the kernels."""
 
-    def __init__(self, shape):
-        self.c = B.make_case(shape)
-        self.shape, self.rows, self.C = shape, self.c["rows"], shape[1]
+    def __init__(self, shape, rep=0):
+        self.c = B.make_case(shape, rep)
+        self.shape, self.rep, self.rows, self.C = shape, rep, self.c["rows"], shape[1]
         for k in ("x", "dy", "res", "dsx"):
             setattr(self, k, self.c[k].cuda())
             setattr(self, k + "b", _dev(self.c[k]))
@@ -55,6 +55,20 @@ class Case:
         B.check_finalize(what, s, q, self.rows, self.gamma, self.beta, self.rm, self.rv,
                          (mean, invstd, coef, rm, rv, 5, int(nbt)))
 
+
+def _same_bits(got, exp, what):
+    """Two outputs of two launches agree bit for bit (the raw patterns: neither is a rounded reference)."""
+    assert got.dtype == exp.dtype and got.shape == exp.shape, what
+    v = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[got.element_size()]
+    bad = got.contiguous().view(v) != exp.contiguous().view(v)
+    assert not bad.any(), "%s: %d of %d elements differ; first at %s" % (
+        what, int(bad.sum()), bad.numel(), bad.nonzero()[0].tolist())
+
+
+# the batched launches: the three BNs of different C, a full batch of kBnFinMax = 8, and a batch of one
+ONE_BN = [((3, 48, 5, 7), 0)]
+FIN_BATCHES = {"three": [(s, 0) for s in B.MULTI_FWD], "eight": B.MULTI8_FWD, "one": ONE_BN}
+BWD_BATCHES = {"three": [(s, 0) for s in B.MULTI_BWD], "eight": B.MULTI8_BWD, "one": ONE_BN}
 
 FWD_VARIANTS = [("plain", False, False, False), ("relu", True, False, False), ("res", False, True, False),
                 ("res_relu", True, True, False), ("res_coef", True, False, True)]
@@ -122,18 +136,31 @@ def test_forward_from_slot_sums(H, shape):
     assert n == 2
 
 
-def test_finalize_multi(H):
-    """bn_finalize_multi: three BNs of different C finalized by one launch (the narrower ones exit early in
-    the blocks past their C), then applied through bn_forward(pre=...), which must not finalize again."""
-    ks = [Case(s) for s in B.MULTI_FWD]
+@pytest.mark.parametrize("batch", list(FIN_BATCHES))
+def test_finalize_multi(H, batch):
+    """bn_finalize_multi: several BNs of different C finalized by one launch (the narrower ones exit early in
+    the blocks past their C), then applied through bn_forward(pre=...), which must not finalize again.
+    A batch of one must give, bit for bit, what the single launch of bn_forward(sums=...) gives: the two
+    entry points run one body."""
+    ks = [Case(s, r) for s, r in FIN_BATCHES[batch]]
+    nb = len(ks)
+    assert nb == {"three": 3, "eight": 8, "one": 1}[batch] and (nb < 8 or ks[-1].C < max(k.C for k in ks))
     st = [k.stats() for k in ks]
-    wss = [B.split_slots(*B.fwd_sums(k.dsx), ("multi", k.shape)) for k in ks]  # not the sums of the xs passed
+    # not the sums of the xs passed
+    wss = [B.split_slots(*B.fwd_sums(k.dsx), ("multi", k.shape) + ((k.rep,) if k.rep else ())) for k in ks]
+    single = None
+    if nb == 1:
+        rm1, rv1, nbt1 = ks[0].stats()
+        ws1 = wss[0].clone()
+        k = ks[0]
+        single = H.bn_forward(k.xb, None, k.gamma, k.beta, rm1, rv1, MOM, EPS, True, True, nbt1, ws1)[:4]
+        single += [rm1, rv1, nbt1, ws1]
     outs = H.bn_finalize_multi([k.xb for k in ks], wss, [k.gamma for k in ks], [k.beta for k in ks],
-                               [s[0] for s in st], [s[1] for s in st], [s[2] for s in st], [MOM] * 3, [EPS] * 3)
-    assert len(outs) == 3
+                               [s[0] for s in st], [s[1] for s in st], [s[2] for s in st], [MOM] * nb, [EPS] * nb)
+    assert len(outs) == nb
     n = 0
     for k, (rm, rv, nbt), ws, (mean, invstd, coef) in zip(ks, st, wss, outs):
-        what = "multi %s" % (k.shape,)
+        what = "multi %s %s" % (k.shape, k.rep)
         k.check_finalize(what, mean, invstd, coef, rm, rv, nbt, k.dsx)
         assert not ws.any(), what + ": the slots are not re-zeroed"
         rm1, rv1, coef1 = rm.clone(), rv.clone(), coef.clone()
@@ -141,8 +168,12 @@ def test_finalize_multi(H):
                          [mean, invstd, coef])[0]
         assert torch.equal(rm, rm1) and torch.equal(rv, rv1) and torch.equal(coef, coef1) and int(nbt) == 6, what
         B.check_fwd_apply(what, k.x, coef, y, True)
+        if single is not None:
+            names = ("y", "mean", "invstd", "coef", "running_mean", "running_var", "num_batches", "sums")
+            for name, got, exp in zip(names, (y, mean, invstd, coef, rm, rv, nbt, ws), single):
+                _same_bits(got, exp, "batch of one against the single launch: " + name)
         n += 1
-    assert n == 3
+    assert n == nb
 
 
 @pytest.mark.parametrize("shape", [(3, 48, 5, 7), (3, 128, 5, 7), (1, 64, 1, 1)], ids=str)
@@ -231,21 +262,33 @@ def test_backward(H, shape):
     assert n == 7
 
 
-def test_backward_multi(H):
-    """bn_backward_multi with mixed widths (two BNs narrower than the widest: their finalize blocks past C exit
-    early), one of the gradients a channel slice of a wider tensor."""
-    ks = [Case(s) for s in B.MULTI_BWD]
-    N, _, Hh, W = B.MULTI_BWD[0]
+@pytest.mark.parametrize("batch", list(BWD_BATCHES))
+def test_backward_multi(H, batch):
+    """bn_backward_multi with mixed widths (BNs narrower than the widest: their finalize blocks past C exit
+    early), one of the gradients a channel slice of a wider tensor.  A batch of one must give, bit for bit,
+    what bn_backward gives: the batched and the single finalize run one body."""
+    ks = [Case(s, r) for s, r in BWD_BATCHES[batch]]
+    nb = len(ks)
+    assert nb == {"three": 3, "eight": 8, "one": 1}[batch] and (nb < 8 or ks[-1].C < max(k.C for k in ks))
+    i48 = [k.C for k in ks].index(48)
+    N, _, Hh, W = ks[i48].shape
     big = torch.full((N, 48 + 24, Hh, W), 3.0, device="cuda", dtype=torch.bfloat16).contiguous(memory_format=CL)
-    big[:, 8:56] = ks[0].dyb
-    dys = [big[:, 8:56], ks[1].dyb, ks[2].dyb]
+    big[:, 8:56] = ks[i48].dyb
+    dys = [k.dyb for k in ks]
+    dys[i48] = big[:, 8:56]
     outs = H.bn_backward_multi(dys, [k.xb for k in ks], [k.mean for k in ks], [k.invstd for k in ks],
                                [k.gamma for k in ks], [k.fcoef for k in ks])
+    assert len(outs) == nb
     n = 0
     for k, (dx, dg, db) in zip(ks, outs):
-        B.check_bwd("multi %s" % (k.shape,), k.c, "cuda", (dx, None, dg, db), True)
+        B.check_bwd("multi %s %s" % (k.shape, k.rep), k.c, "cuda", (dx, None, dg, db), True)
         n += 1
-    assert n == 3
+    assert n == nb
+    if nb == 1:
+        k = ks[0]
+        dx1, _, dg1, db1 = H.bn_backward(dys[0], k.xb, k.mean, k.invstd, k.gamma, k.fcoef, None, True, True, False)
+        for name, got, exp in zip(("dx", "dgamma", "dbeta"), outs[0], (dx1, dg1, db1)):
+            _same_bits(got, exp, "batch of one against bn_backward: " + name)
 
 
 # ---- stem: BN + ReLU + MaxPool(3, 2, 1) ------------------------------------------------------------
