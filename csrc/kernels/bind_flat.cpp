@@ -66,6 +66,127 @@ void adam_step(at::Tensor w, at::Tensor g, at::Tensor m, at::Tensor v, double lr
                      step.data_ptr<float>(), stream_of(w, 0), sh);
 }
 
+// The slot / chunk tables of lars_step and lamb_step.  offsets is a host int64 tensor of nseg + 1 slot
+// starts (read here, on every call: a few hundred words); everything else lives on w's device.
+kfk::LayerTables layer_tables(const char *op, const at::Tensor &w, const at::Tensor &offsets, const at::Tensor &chunks,
+                              const at::Tensor &slot_chunk0, const at::Tensor &partials, const at::Tensor &wd_tab,
+                              const at::Tensor &trust_tab, const at::Tensor &w_norm, const at::Tensor &x_norm,
+                              const at::Tensor &ratio) {
+    TORCH_CHECK(offsets.device().is_cpu() && offsets.scalar_type() == at::kLong && offsets.dim() == 1 &&
+                    offsets.is_contiguous() && offsets.numel() >= 2,
+                op, ": offsets must be a host int64 vector of nseg + 1 slot starts");
+    const int64_t *off = offsets.data_ptr<int64_t>();
+    const int64_t nseg = offsets.numel() - 1;
+    TORCH_CHECK(off[0] == 0 && off[nseg] == w.numel(), op, ": offsets must start at 0 and end at numel (", w.numel(),
+                ")");
+    int64_t nchunks = 0;
+    for (int64_t k = 0; k < nseg; ++k) {
+        TORCH_CHECK(off[k + 1] > off[k], op, ": offsets must be ascending (slot ", k, ")");
+        TORCH_CHECK(off[k + 1] % 64 == 0, op, ": offsets must be multiples of 64 (slot ", k + 1, ")");
+        nchunks += (off[k + 1] - off[k] + kfk::kLayerChunk - 1) / kfk::kLayerChunk;
+    }
+    const Dev dev = w.device();
+    TORCH_CHECK(chunks.dim() == 2 && chunks.size(1) == 3, op, ": chunks must be an int64 [", nchunks, ", 3] tensor");
+    check_dense(chunks, op, "chunks", dev, at::kLong, 3 * nchunks);
+    check_dense(slot_chunk0, op, "slot_chunk0", dev, at::kLong, nseg + 1);
+    check_dense(partials, op, "partials", dev, at::kFloat, 2 * nchunks);
+    check_dense(wd_tab, op, "wd_tab", dev, at::kFloat, nseg);
+    check_dense(trust_tab, op, "trust_tab", dev, at::kFloat, nseg);
+    check_dense(w_norm, op, "w_norm", dev, at::kFloat, nseg);
+    check_dense(x_norm, op, "x_norm", dev, at::kFloat, nseg);
+    check_dense(ratio, op, "ratio", dev, at::kFloat, nseg);
+    kfk::LayerTables t;
+    t.chunks = chunks.data_ptr<int64_t>();
+    t.slot_chunk0 = slot_chunk0.data_ptr<int64_t>();
+    t.nchunks = narrow(nchunks, op, "the chunk count");
+    t.nseg = narrow(nseg, op, "the slot count");
+    t.partials = partials.data_ptr<float>();
+    t.wd_tab = wd_tab.data_ptr<float>();
+    t.trust_tab = trust_tab.data_ptr<float>();
+    t.w_norm = w_norm.data_ptr<float>();
+    t.x_norm = x_norm.data_ptr<float>();
+    t.ratio = ratio.data_ptr<float>();
+    return t;
+}
+
+// the layer-wise kernels move float4s: a view that starts inside a 16-byte word is refused
+void check_flat_f32(const at::Tensor &t, const char *op, const char *name, const at::Tensor &w) {
+    check_dense(t, op, name, w.device(), at::kFloat, w.numel());
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, op, ": ", name, " must be 16-byte aligned");
+}
+
+const float *lr_ptr(const char *op, const OptTensor &lr_t, const Dev &dev) {
+    if (!has(lr_t)) return nullptr;
+    check_dense(*lr_t, op, "lr_t", dev, at::kFloat, 1);
+    return lr_t->data_ptr<float>();
+}
+
+uint16_t *shadow_ptr(const char *op, const OptTensor &shadow, const at::Tensor &w) {
+    if (!has(shadow)) return nullptr;
+    check_dense(*shadow, op, "shadow", w.device(), at::kBFloat16, w.numel());
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(shadow->data_ptr()) % 8 == 0, op, ": shadow must be 8-byte aligned");
+    return bf16_mut(*shadow);
+}
+
+void lars_step(at::Tensor w, at::Tensor g, OptTensor m, OptTensor shadow, at::Tensor offsets, at::Tensor chunks,
+               at::Tensor slot_chunk0, at::Tensor partials, at::Tensor wd_tab, at::Tensor trust_tab, at::Tensor w_norm,
+               at::Tensor x_norm, at::Tensor ratio, double lr, OptTensor lr_t, double mu, double tc, double eps,
+               double gscale, bool nesterov) {
+    const char *op = "lars_step";
+    check_gpu(w, "lars_step: w");
+    check_flat_f32(w, op, "w", w);
+    check_flat_f32(g, op, "g", w);
+    float *mp = nullptr;
+    if (has(m)) {
+        check_flat_f32(*m, op, "m", w);
+        mp = m->data_ptr<float>();
+    }
+    TORCH_CHECK(mu == 0.0 || mp, op, ": m must be given with a momentum");
+    uint16_t *sp = shadow_ptr(op, shadow, w);
+    const float *lrp = lr_ptr(op, lr_t, w.device());
+    const auto t = layer_tables(op, w, offsets, chunks, slot_chunk0, partials, wd_tab, trust_tab, w_norm, x_norm, ratio);
+    c10::DeviceGuard gd(w.device());
+    kfk::launch_lars(w.data_ptr<float>(), g.data_ptr<float>(), mp, sp, w.numel(), t, static_cast<float>(lr), lrp,
+                     static_cast<float>(mu), static_cast<float>(tc), static_cast<float>(eps),
+                     static_cast<float>(gscale), nesterov, stream_of(w, 0));
+}
+
+// max_grad_norm <= 0: no clipping; else gnorm_ws (f32, 2 * grid cap + 2 words) is the scratch of the
+// sum-of-squares pass over g that runs ahead of the partial-norm stage.
+void lamb_step(at::Tensor w, at::Tensor g, at::Tensor m, at::Tensor v, OptTensor shadow, at::Tensor offsets,
+               at::Tensor chunks, at::Tensor slot_chunk0, at::Tensor partials, at::Tensor wd_tab, at::Tensor trust_tab,
+               at::Tensor w_norm, at::Tensor x_norm, at::Tensor ratio, double lr, OptTensor lr_t, double b1, double b2,
+               double eps, double gscale, at::Tensor step, bool bias_correction, double max_grad_norm,
+               OptTensor gnorm_ws) {
+    const char *op = "lamb_step";
+    check_gpu(w, "lamb_step: w");
+    check_flat_f32(w, op, "w", w);
+    check_flat_f32(g, op, "g", w);
+    check_flat_f32(m, op, "m", w);
+    check_flat_f32(v, op, "v", w);
+    check_dense(step, op, "step", w.device(), at::kFloat, 1);
+    uint16_t *sp = shadow_ptr(op, shadow, w);
+    const float *lrp = lr_ptr(op, lr_t, w.device());
+    const auto t = layer_tables(op, w, offsets, chunks, slot_chunk0, partials, wd_tab, trust_tab, w_norm, x_norm, ratio);
+    float *ws = nullptr;
+    if (max_grad_norm > 0.0) {
+        TORCH_CHECK(has(gnorm_ws), op, ": gnorm_ws must be given with max_grad_norm");
+        check_dense(*gnorm_ws, op, "gnorm_ws", w.device(), at::kFloat, 2 * kfk::kMaxGridHost + 2);
+        ws = gnorm_ws->data_ptr<float>();
+    }
+    c10::DeviceGuard gd(w.device());
+    auto s = stream_of(w, 0);
+    const float *gsq = nullptr;
+    if (ws) {
+        float *out = ws + 2 * kfk::kMaxGridHost;
+        kfk::launch_sumsq2(g.data_ptr<float>(), nullptr, w.numel(), dtype_code(g), ws, out, s);
+        gsq = out;
+    }
+    kfk::launch_lamb(w.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), sp, w.numel(),
+                     t, static_cast<float>(lr), lrp, b1, b2, static_cast<float>(eps), static_cast<float>(gscale),
+                     step.data_ptr<float>(), bias_correction, static_cast<float>(max_grad_norm), gsq, s);
+}
+
 void axpby(at::Tensor y, at::Tensor x, OptTensor z, double a, double b) {
     check_gpu(y, "y");
     check_gpu(x, "x");
@@ -256,6 +377,20 @@ void bind_flat(py::module_ &m) {
           py::arg("w"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("lr"), py::arg("lr_t"), py::arg("b1"),
           py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("adamw"), py::arg("gscale"), py::arg("step"),
           py::arg("shadow") = py::none());
+    m.def("lars_step", &lars_step, "fused LARS step on a flat f32 space: per-slot norms, trust ratio, apply",
+          py::arg("w"), py::arg("g"), py::arg("m"), py::arg("shadow"), py::arg("offsets"), py::arg("chunks"),
+          py::arg("slot_chunk0"), py::arg("partials"), py::arg("wd_tab"), py::arg("trust_tab"), py::arg("w_norm"),
+          py::arg("x_norm"), py::arg("ratio"), py::arg("lr"), py::arg("lr_t"), py::arg("mu"), py::arg("tc"),
+          py::arg("eps"), py::arg("gscale"), py::arg("nesterov"));
+    m.def("lamb_step", &lamb_step, "fused LAMB step on a flat f32 space: moments + per-slot norms, trust ratio, apply",
+          py::arg("w"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("shadow"), py::arg("offsets"),
+          py::arg("chunks"), py::arg("slot_chunk0"), py::arg("partials"), py::arg("wd_tab"), py::arg("trust_tab"),
+          py::arg("w_norm"), py::arg("x_norm"), py::arg("ratio"), py::arg("lr"), py::arg("lr_t"), py::arg("b1"),
+          py::arg("b2"), py::arg("eps"), py::arg("gscale"), py::arg("step"), py::arg("bias_correction"),
+          py::arg("max_grad_norm") = 0.0, py::arg("gnorm_ws") = py::none());
+    // elements per chunk of the layer-wise kernels and the cap of their chunk-loop grid
+    m.attr("layerwise_chunk") = kfk::kLayerChunk;
+    m.attr("layerwise_grid_cap") = kfk::kLayerGridCap;
     m.def("axpby", &axpby, "y = a*y + b*x (optionally also z = y)", py::arg("y"), py::arg("x"), py::arg("z"),
           py::arg("a"), py::arg("b"));
     m.def("scale_", &scale_, "x *= alpha");

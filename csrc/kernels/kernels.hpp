@@ -71,6 +71,36 @@ void launch_adam(float *w, const float *g, float *m, float *v, size_t n, float l
                  float b2, float eps, float wd, bool adamw, float gscale, const float *step_dev, hipStream_t s,
                  uint16_t *shadow = nullptr);
 
+// layerwise.hip: LARS / LAMB on a flat space whose slots (tensors with their alignment padding) start at
+// multiples of 64 elements.  A step is three launches on `s` with fixed shapes: per-chunk partial sums
+// of squares, per-slot norms and trust ratio, apply.  A chunk is at most kLayerChunk elements of ONE
+// slot; chunks[c] = {first element, slot, length} and slot_chunk0[k] = first chunk of slot k (nseg + 1
+// entries) are device tables built once by the caller; partials holds 2 floats per chunk.  w_norm,
+// x_norm, ratio (nseg floats each) receive ||w||, ||g|| (LARS) or ||u|| (LAMB) and the ratio applied.
+// wd_tab / trust_tab: per-slot weight decay and 0 / 1 trust switch.  No float atomics: every sum has
+// a fixed order.  lr is read from *lr_dev when given, as in launch_sgd.
+constexpr int kLayerChunk = 4096;
+constexpr int kLayerGridCap = 2048;
+struct LayerTables {
+    const int64_t *chunks;       // [nchunks][3]
+    const int64_t *slot_chunk0;  // [nseg + 1]
+    int nchunks, nseg;
+    float *partials;             // [nchunks][2]
+    const float *wd_tab, *trust_tab;
+    float *w_norm, *x_norm, *ratio;
+};
+//   q = trust ? tc*||w|| / (||g|| + wd*||w|| + eps) : 1 ; d = q*(g*gscale + wd*w) ; m = mu*m + d ;
+//   w -= lr * (nesterov ? d + mu*m : m).  m may be null when mu == 0.
+void launch_lars(float *w, const float *g, float *m, uint16_t *shadow, size_t n, const LayerTables &t, float lr,
+                 const float *lr_dev, float mu, float tc, float eps, float gscale, bool nesterov, hipStream_t s);
+//   g' = g*gscale*clip ; m = b1*m + (1-b1)*g' ; v = b2*v + (1-b2)*g'^2 ; u = mhat/(sqrt(vhat)+eps) + wd*w ;
+//   r = trust ? ||w||/||u|| : 1 ; w -= lr*r*u.  step_dev: the step count, already incremented (bias
+//   correction on device, in f64, when bias_correction).  gsq (optional): device sum of squares of the
+//   unscaled gradient; clip = min(1, max_grad_norm / (|gscale| * sqrt(*gsq))).
+void launch_lamb(float *w, const float *g, float *m, float *v, uint16_t *shadow, size_t n, const LayerTables &t,
+                 float lr, const float *lr_dev, double b1, double b2, float eps, float gscale, const float *step_dev,
+                 bool bias_correction, float max_grad_norm, const float *gsq, hipStream_t s);
+
 // K3/K4: y = a*y + b*x (f32 or bf16), optionally also writing the result to z.
 void launch_axpby(void *y, const void *x, void *z, size_t n, float a, float b, int dtype, hipStream_t s);
 

@@ -8,6 +8,7 @@ MonitorGradientVarianceOptimizer) and ``srcs/python/kungfu/torch/optimizers``.
 from .ada_sgd import AdaptiveSGDOptimizer
 from .core import KungFuOptimizer
 from .fused import FusedAdam, FusedSGD
+from .layerwise import LAMB, LARS, FusedLAMB, FusedLARS
 from .monitors import MonitorGradientNoiseScaleOptimizer, MonitorGradientVarianceOptimizer
 from .pair_avg import PairAveragingOptimizer
 from .sma import SynchronousAveragingOptimizer

@@ -12,7 +12,9 @@ A wrapper is itself a ``torch.optim.Optimizer`` whose ``param_groups`` and
 On GPU the wrapper re-homes the parameters into a :class:`FlatParamSpace`
 (one flat f32 param buffer + one flat grad buffer); plain ``torch.optim.SGD``
 / ``Adam`` / ``AdamW`` with a single param group are replaced by the fused
-flat-buffer HIP optimizers unless ``fused=False``.
+flat-buffer HIP optimizers unless ``fused=False``; so are ``LARS`` / ``LAMB``
+(``optimizers/layerwise.py``), whose groups may differ in ``weight_decay`` /
+``trust``.
 """
 from __future__ import annotations
 
@@ -23,6 +25,7 @@ import torch
 from ..parallel.flat import FlatParamSpace
 from ..utils import trace
 from .fused import FusedAdam, FusedSGD
+from .layerwise import LAMB, LARS, fused_from
 
 
 def _named(named_parameters, optimizer) -> dict:
@@ -35,6 +38,8 @@ def _named(named_parameters, optimizer) -> dict:
 
 def make_fused(optimizer: torch.optim.Optimizer, space: FlatParamSpace) -> Optional[torch.optim.Optimizer]:
     """Build a fused flat optimizer equivalent to ``optimizer`` if possible."""
+    if type(optimizer) in (LARS, LAMB):  # per-slot weight decay / trust: several groups are fine
+        return fused_from(optimizer, space)
     if len(optimizer.param_groups) != 1:
         return None
     g = optimizer.param_groups[0]
