@@ -101,29 +101,34 @@ at::Tensor colsum(at::Tensor x, at::ScalarType dtype) {
     return out;
 }
 
-// contiguous bf16 [B, S, 3*H*64] with S in {64, 128}: {B, S, H}
-std::tuple<int, int, int> check_qkv(const at::Tensor &qkv, int64_t heads, const char *op) {
+// contiguous bf16 [B, S, 3*H*64] with S a multiple of 64 up to 512: {B, S, H}
+// (stream_kernel, the streaming kernels at S = 128 for tests, is refused where they do not exist: S = 64)
+std::tuple<int, int, int> check_qkv(const at::Tensor &qkv, int64_t heads, const char *op, bool stream_kernel) {
     check_dense(qkv, op, "qkv", kAnyGpu, at::kBFloat16, qkv.numel());
     TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == 3 * heads * 64 && kfk::attention_supported(qkv.size(1), 64), op,
-                ": qkv must be [B, S, 3*H*64] with S in {64, 128}");
+                ": qkv must be [B, S, 3*H*64] with S ", kfk::kAttentionLengths);
+    TORCH_CHECK(!stream_kernel || qkv.size(1) >= 128, op, ": stream_kernel needs S >= 128");
     return {narrow(qkv.size(0), op, "B"), narrow(qkv.size(1), op, "S"), narrow(heads, op, "heads")};
 }
 
 // Fused self-attention: qkv [B, S, 3*H*64] bf16 contiguous -> (out [B, S, H*64] bf16, lse [B, H, S] f32)
-std::vector<at::Tensor> attention_forward(at::Tensor qkv, int64_t heads, double scale, int64_t seed, double p_drop) {
-    const auto [B, S, H] = check_qkv(qkv, heads, "attention_forward");
+// stream_kernel: S = 128 on the streaming kernels of attention_long.hip (S > 128 always runs them)
+std::vector<at::Tensor> attention_forward(at::Tensor qkv, int64_t heads, double scale, int64_t seed, double p_drop,
+                                          bool stream_kernel) {
+    const auto [B, S, H] = check_qkv(qkv, heads, "attention_forward", stream_kernel);
     c10::DeviceGuard gd(qkv.device());
     auto out = at::empty({B, S, H * 64}, qkv.options());
     auto lse = at::empty({B, H, S}, qkv.options().dtype(at::kFloat));
     kfk::launch_attention_forward(bf16(qkv), bf16_mut(out), lse.data_ptr<float>(), B, S, H, static_cast<float>(scale),
-                                  static_cast<uint32_t>(seed), static_cast<float>(p_drop), stream_of(qkv, 0));
+                                  static_cast<uint32_t>(seed), static_cast<float>(p_drop), stream_of(qkv, 0),
+                                  stream_kernel);
     return {out, lse};
 }
 
 at::Tensor attention_backward(at::Tensor qkv, at::Tensor out, at::Tensor lse, at::Tensor dout, int64_t heads,
-                              double scale, int64_t seed, double p_drop) {
+                              double scale, int64_t seed, double p_drop, bool stream_kernel) {
     const char *op = "attention_backward";
-    const auto [B, S, H] = check_qkv(qkv, heads, op);
+    const auto [B, S, H] = check_qkv(qkv, heads, op, stream_kernel);
     const Dev dev = qkv.device();
     check_dense(out, op, "out", dev, at::kBFloat16, out.numel());
     TORCH_CHECK(out.sizes() == at::IntArrayRef({B, S, H * 64}),
@@ -135,9 +140,12 @@ at::Tensor attention_backward(at::Tensor qkv, at::Tensor out, at::Tensor lse, at
     c10::DeviceGuard gd(qkv.device());
     if (!dout.is_contiguous()) dout = dout.contiguous();
     auto dqkv = at::empty_like(qkv);
+    // rowsum(dO o O): the streaming dQ kernel fills it for the dK/dV kernel
+    at::Tensor dsum;
+    if (S > 128 || stream_kernel) dsum = at::empty({B, H, S}, lse.options());
     kfk::launch_attention_backward(bf16(qkv), bf16(out), lse.data_ptr<float>(), bf16(dout), bf16_mut(dqkv), B, S, H,
                                    static_cast<float>(scale), static_cast<uint32_t>(seed), static_cast<float>(p_drop),
-                                   stream_of(qkv, 0));
+                                   stream_of(qkv, 0), dsum.defined() ? dsum.data_ptr<float>() : nullptr, stream_kernel);
     return dqkv;
 }
 
@@ -306,11 +314,14 @@ void bind_bert(py::module_ &m) {
           py::arg("s"), py::arg("gamma"), py::arg("mean"), py::arg("rstd"), py::arg("p") = 0.0, py::arg("seed") = 0,
           py::arg("rbias_dtype") = py::none());
     m.def("attention_supported", &kfk::attention_supported);
-    m.def("attention_forward", &attention_forward, "fused self-attention forward (S 64/128, head dim 64, dropout)",
-          py::arg("qkv"), py::arg("heads"), py::arg("scale"), py::arg("seed"), py::arg("p_drop"));
-    m.def("attention_backward", &attention_backward, "fused self-attention backward -> dqkv", py::arg("qkv"),
-          py::arg("out"), py::arg("lse"), py::arg("dout"), py::arg("heads"), py::arg("scale"), py::arg("seed"),
-          py::arg("p_drop"));
+    m.def("attention_forward", &attention_forward,
+          "fused self-attention forward (S 64..512 in steps of 64, head dim 64, dropout) -> (out, lse); "
+          "stream_kernel: S = 128 on the streaming kernels that serve S > 128",
+          py::arg("qkv"), py::arg("heads"), py::arg("scale"), py::arg("seed"), py::arg("p_drop"),
+          py::arg("stream_kernel") = false);
+    m.def("attention_backward", &attention_backward, "fused self-attention backward -> dqkv (S as the forward)",
+          py::arg("qkv"), py::arg("out"), py::arg("lse"), py::arg("dout"), py::arg("heads"), py::arg("scale"),
+          py::arg("seed"), py::arg("p_drop"), py::arg("stream_kernel") = false);
     m.def("gemm_nt", &gemm_nt, py::arg("a"), py::arg("b"), py::arg("bias") = py::none(), py::arg("out") = py::none(),
           py::arg("accumulate") = false, py::arg("bn") = -1,
           "bf16 a[M,K] . b[N,K]^T (+bias) (+out) on the pipelined 256 x bn MFMA GEMM (gemm.hip)");

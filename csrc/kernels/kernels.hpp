@@ -501,15 +501,19 @@ void launch_layernorm_backward(const uint16_t *dy, const uint16_t *s, const floa
 void launch_maxpool2x2_backward(const uint16_t *x, const uint16_t *dy, uint16_t *dx, int64_t N, int H, int W, int C,
                                 hipStream_t s, double *gate_stats = nullptr);
 
-// Fused self-attention (attention.hip): qkv [B, S, 3, H, 64] bf16 (the fused projection's
-// output), out [B, S, H*64] bf16, lse [B, H, S] f32; dropout p_drop on the probabilities from a
-// counter hash of (seed, b*H + h, query, key); S = 64 or 128, head dim 64, no mask.
+// Fused self-attention: qkv [B, S, 3, H, 64] bf16 (the fused projection's output), out
+// [B, S, H*64] bf16, lse [B, H, S] f32; dropout p_drop on the probabilities from a counter hash
+// of (seed, b*H + h, query, key); head dim 64, no mask.  S = 64 or 128 runs the whole-sequence
+// kernels of attention.hip, every multiple of 64 from 192 to 512 the streaming kernels of
+// attention_long.hip; stream_kernel sends S = 128 to the streaming kernels too (for tests; refused at S = 64).
 bool attention_supported(int S, int head_dim);
+constexpr const char *kAttentionLengths = "64, 128, 192, 256, 320, 384, 448 or 512";  // the one spelling of the set
 void launch_attention_forward(const uint16_t *qkv, uint16_t *out, float *lse, int B, int S, int H, float scale,
-                              uint32_t seed, float p_drop, hipStream_t s);
-// dqkv [B, S, 3, H, 64] (every element written)
+                              uint32_t seed, float p_drop, hipStream_t s, bool stream_kernel = false);
+// dqkv [B, S, 3, H, 64] (every element written); dsum: [B, H, S] f32 scratch, needed (and only
+// touched) by the streaming kernels
 void launch_attention_backward(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *dout,
                                uint16_t *dqkv, int B, int S, int H, float scale, uint32_t seed, float p_drop,
-                               hipStream_t s);
+                               hipStream_t s, float *dsum = nullptr, bool stream_kernel = false);
 
 }  // namespace kfk

@@ -95,6 +95,7 @@ KNOBS: Dict[str, Knob] = {
     "KUNGFU_WGRAD_RECT": _u("1", "rectangular-window weight gradients on the MFMA kernels"),
     "KUNGFU_FUSED_BLOCK": _u("1", "ResNet bottleneck as one fused autograd node"),
     "KUNGFU_STEM": _u("1", "image stem convs (ResNet 7x7, Inception Conv2d_1a, VGG first layer) on the MFMA stem kernels"),
+    "KUNGFU_ATTN_LONG": _u("1", "self-attention of 192 to 512 tokens on the streaming attention kernels (0: torch SDPA)"),
     "KUNGFU_LINEAR_WGRAD": _u("1", "linear-layer weight gradients on the split-K MFMA kernel"),
     "KUNGFU_DEV_KNOBS": _u("0", "1: honour the dev (A/B) knobs below"),
     # -- launcher / worker env contract (csrc/launcher/job.cpp, csrc/runtime/peer.cpp) ---------

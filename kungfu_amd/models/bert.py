@@ -1,8 +1,8 @@
 """BERT-base encoder for masked-LM pre-training throughput (BASELINE.json config 5:
 "BERT-base SynchronousSGD + gradient-noise-scale monitor + elastic resize").
 12 layers, hidden 768, 12 heads, FFN 3072, vocab 30522, ~110 M parameters.
-Attention: the fused HIP kernels of ops/attention.py (S 64/128, no mask), else torch's
-scaled_dot_product_attention."""
+Attention: the fused HIP kernels of ops/attention.py (S 64 .. 512 in steps of 64, no mask), else
+torch's scaled_dot_product_attention (also for S > 128 with KUNGFU_ATTN_LONG=0)."""
 import math
 
 import torch

@@ -1,4 +1,6 @@
-"""Fused multi-head self-attention on the HIP kernels of csrc/kernels/attention.hip.
+"""Fused multi-head self-attention on the HIP kernels of csrc/kernels/attention.hip (S = 64 or
+128: the whole sequence in LDS) and csrc/kernels/attention_long.hip (S = 192 .. 512 in steps of
+64: a resident row block, streamed column blocks, online softmax).
 
 ``self_attention(qkv, heads, p)`` takes the fused q/k/v projection output ``[B, S, 3*H*64]``
 (the ``[B, S, 3, H, 64]`` layout of one ``nn.Linear(d, 3d)``) and returns the attention output
@@ -8,12 +10,14 @@ gradient (no concatenation).  Dropout on the attention probabilities uses a coun
 (seed, b*H + h, query, key) -- the mask is recomputed in the backward, never stored;
 :func:`dropout_keep` reproduces it in torch for the tests.
 
-Covers BERT's shapes (S = 64 or 128 tokens, head dim 64, no attention mask); anything else
-runs ``F.scaled_dot_product_attention``.
+Covers BERT's shapes (S a multiple of 64 up to 512 tokens, head dim 64, no attention mask);
+anything else runs ``F.scaled_dot_product_attention``, and so does S > 128 with
+``KUNGFU_ATTN_LONG=0``.
 """
 from __future__ import annotations
 
 import math
+import os
 
 import torch
 import torch.nn.functional as F
@@ -24,6 +28,10 @@ from . import dropout_seed
 # (round 6: the qkv bias gradient from column sums inside the attention backward is gone -- measured slower
 # end to end than the projection's own two-stage column sum, BERT-base + GNS 15.70-15.76 -> 15.78-15.80
 # ms/step on one box, r5t38)
+
+
+# 0: sequences longer than 128 tokens go back to F.scaled_dot_product_attention
+_LONG_ENABLED = os.environ.get("KUNGFU_ATTN_LONG", "1") != "0"
 
 
 class _AttnFn(torch.autograd.Function):
@@ -44,7 +52,8 @@ class _AttnFn(torch.autograd.Function):
 
 def eligible(qkv: torch.Tensor, heads: int) -> bool:
     return (qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.dim() == 3 and qkv.is_contiguous()
-            and qkv.shape[2] == 3 * heads * 64 and hip_available() and hip().attention_supported(int(qkv.shape[1]), 64))
+            and qkv.shape[2] == 3 * heads * 64 and (_LONG_ENABLED or qkv.shape[1] <= 128)
+            and hip_available() and hip().attention_supported(int(qkv.shape[1]), 64))
 
 
 def self_attention(qkv: torch.Tensor, heads: int, p: float = 0.0) -> torch.Tensor:
