@@ -147,6 +147,10 @@ build/wgrad_plan_dump: $(WP_SRCS) csrc/kernels/wgrad_plan.hpp
 build/wgrad_plan_dump_asan: $(WP_SRCS) csrc/kernels/wgrad_plan.hpp
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) -Icsrc/kernels -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -o $@ $(WP_SRCS)
+# the conv kernels' reciprocal division on the CPU (tests/test_rounding_cases.py)
+build/recip_div_check: tests/native/recip_div_check.cpp csrc/kernels/recip_div.hpp
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) -Icsrc/kernels -g -o $@ $<
 native-test: build/native_test
 	./build/native_test
 native-test-asan: build/native_test_asan

@@ -42,11 +42,16 @@ inline int grid_for(size_t n_vec) {
 
 __device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float(static_cast<uint32_t>(h) << 16); }
 
-// f32 -> bf16, round to nearest even (finite inputs; NaN payloads are not preserved).  Integer
-// rounding, NOT gfx950's v_cvt_pk_bf16_f32: the same bits for every finite input
-// (tools/diag/cvt_check.hip, 2^26 patterns), but the instruction measured far slower in the kernels
-// -- the NT GEMM with it 6.5x slower (101.7 vs 15.7 ms over 108 launches), ResNet-50 21.17 vs
-// 20.35 ms/step, BERT-base 26.8 vs 15.95 ms/step (tools/runs/gpu_r6_t13.sh / t14, same box).
+// f32 -> bf16, round to nearest even, in integer arithmetic (about 2.5 vector instructions per
+// value).  Finite inputs and infinities only: a NaN is NOT guaranteed to stay one (0x7f800001
+// rounds to +inf, 0x7fffffff carries into the sign and gives -0).  gfx950's v_cvt_pk_bf16_f32 gives
+// the same bits for every finite input (tools/diag/cvt_check.hip, 2^26 patterns) and is not a slow
+// instruction; what round 6 measured when it replaced this function everywhere through
+// __builtin_convertvector (the NT GEMM 6.5x slower, ResNet-50 21.17 vs 20.35 ms/step) was register
+// allocation: 156-444 bytes of scratch per lane in gemm_nt_kernel<192|256, *>, and in the conv
+// kernels a second accumulator set (96 instead of 64 AGPRs), which took the row-image kernel from
+// two waves per SIMD to one (profiles/conv_epilogue_rounding.md).  So this stays the default, and
+// cvt_pk_bf16 below is used site by site where the kernel's resource line does not get worse.
 __device__ __forceinline__ uint16_t f32_to_bf16(float f) {
     uint32_t u = __float_as_uint(f);
     u += 0x7fffu + ((u >> 16) & 1u);
@@ -55,6 +60,17 @@ __device__ __forceinline__ uint16_t f32_to_bf16(float f) {
 // (lo, hi) -> one 32-bit word, lo in the low half
 __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
     return static_cast<uint32_t>(f32_to_bf16(lo)) | (static_cast<uint32_t>(f32_to_bf16(hi)) << 16);
+}
+// The same pair in ONE instruction, v_cvt_pk_bf16_f32: round to nearest even, bit-identical to
+// pack_bf16x2 for every finite input and the infinities (overflow rounds to +-inf, f32 subnormals
+// to +-0 or the smallest bf16 subnormal, the sign of zero is kept); a NaN input comes out as a NaN
+// (quiet), which the integer formula does not guarantee.  Inline asm with "v" operands, not
+// __builtin_convertvector: the asm reads the accumulators where they are, while the builtin made the
+// compiler keep a second accumulator set in the conv kernels (see f32_to_bf16).
+__device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) {
+    uint32_t r;
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+    return r;
 }
 
 __device__ __forceinline__ float f16_to_f32(uint16_t h) {

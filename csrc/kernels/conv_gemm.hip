@@ -15,13 +15,15 @@ void launch_gemm_t(const uint16_t *x, const uint16_t *w, uint16_t *y, Geo g, con
     if (g.K % BN) throw std::invalid_argument("gemm: out-features not a multiple of the tile");
     g.mtiles = (g.M + BM - 1) / BM;
     g.ntiles = g.K / BN;
+    geo_recip(g);
     check_buf_extent(g);
     const dim3 grid(g.mtiles * g.ntiles), block(64 * WM * WN);
+    // H = W = 1: row m of x is pixel m, always the decode-free A rows (FAST1)
     switch (epi) {
-    case 0: conv_kernel<1, WM, WN, ST, 0, TM, TN><<<grid, block, 0, s>>>(x, w, y, g, ea); break;
-    case kEpiBias: conv_kernel<1, WM, WN, ST, kEpiBias, TM, TN><<<grid, block, 0, s>>>(x, w, y, g, ea); break;
-    case kEpiGeluGrad: conv_kernel<1, WM, WN, ST, kEpiGeluGrad, TM, TN><<<grid, block, 0, s>>>(x, w, y, g, ea); break;
-    case kEpiAccum: conv_kernel<1, WM, WN, ST, kEpiAccum, TM, TN><<<grid, block, 0, s>>>(x, w, y, g, ea); break;
+    case 0: conv_kernel<1, WM, WN, ST, 0, TM, TN, false, true><<<grid, block, 0, s>>>(x, w, y, g, ea); break;
+    case kEpiBias: conv_kernel<1, WM, WN, ST, kEpiBias, TM, TN, false, true><<<grid, block, 0, s>>>(x, w, y, g, ea); break;
+    case kEpiGeluGrad: conv_kernel<1, WM, WN, ST, kEpiGeluGrad, TM, TN, false, true><<<grid, block, 0, s>>>(x, w, y, g, ea); break;
+    case kEpiAccum: conv_kernel<1, WM, WN, ST, kEpiAccum, TM, TN, false, true><<<grid, block, 0, s>>>(x, w, y, g, ea); break;
     default: throw std::invalid_argument("gemm: unsupported epilogue");
     }
 }

@@ -25,12 +25,13 @@
 // with w'[ci, kh, kw, co] = w[co, 2-kh, 2-kw, ci] (conv_flip_weight).
 //
 // This header holds the kernel template and its launch helpers; the instantiations are spread over
-// conv.hip (dispatch, weight flips), conv_k1.hip / conv_k3.hip (square windows), conv_rect.hip,
-// conv_gemm.hip and conv_s2.hip, so the ~480 kernel instances build in parallel.
+// conv.hip (dispatch, weight flips), conv_k1.hip / conv_k1_fast.hip / conv_k3.hip (square windows),
+// conv_rect.hip, conv_gemm.hip and conv_s2.hip, so the ~600 kernel instances build in parallel.
 #pragma once
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "recip_div.hpp"
 
 #include <cstdlib>
 #include <stdexcept>
@@ -51,7 +52,25 @@ struct Geo {
     int ph, pw;  // zero padding (rows, columns)
     int stagger;  // 1: the upper half of 8 waves issues its LDS-DMA staging before its fragment reads
     int prio;     // 1: the upper (second-dispatched) wave half runs at s_setprio 1
+    // multipliers of the pixel decodes (recip_div.hpp; geo_recip fills them at every launch):
+    // m / OW, t / OH, and the row-image kernel's slot / (W + 2), row / (H + 2)
+    uint32_t rOW, rOH, rWp, rHp;
 };
+
+// The reciprocal multipliers of g's divisors, once OH / OW are final (each launcher, per launch).
+inline void geo_recip(Geo &g) {
+    g.rOW = recip_magic(static_cast<uint32_t>(g.OW));
+    g.rOH = recip_magic(static_cast<uint32_t>(g.OH));
+    g.rWp = recip_magic(static_cast<uint32_t>(g.W + 2));
+    g.rHp = recip_magic(static_cast<uint32_t>(g.H + 2));
+}
+
+// A 1x1, stride-1, unpadded convolution onto the pixels of its input: output pixel m reads input
+// pixel m, so the A row of the staging is m * C with no decode and no padding mask (conv_kernel's
+// FAST1 instantiations).  Stride-2 forwards and the scattering data-gradient phases keep the decode.
+inline bool conv_fast1(const Geo &g) {
+    return g.stride == 1 && g.ph == 0 && g.pw == 0 && g.tapmap < 0 && !g.scat && g.OH == g.H && g.OW == g.W;
+}
 
 void check_buf_extent(const Geo &g);
 int conv_tile_rules();
@@ -63,6 +82,9 @@ void launch_conv_k1(const uint16_t *x, const uint16_t *w, uint16_t *y, Geo g, co
                     hipStream_t s, int variant);
 void launch_conv_k3(const uint16_t *x, const uint16_t *w, uint16_t *y, Geo g, const EpiArgs &ea, int epi,
                     hipStream_t s, int variant);
+// the decode-free instances of launch_conv_k1 (conv_k1_fast.hip; conv_fast1(g) must hold)
+void launch_conv_k1_fast(const uint16_t *x, const uint16_t *w, uint16_t *y, Geo g, const EpiArgs &ea, int epi,
+                         hipStream_t s, int variant);
 
 namespace {
 
@@ -70,6 +92,20 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 __device__ __forceinline__ int wm_of(int wave, int wn) { return wave / wn; }
+
+// Output pixel m -> (n, oh, ow) with the launch's reciprocal multipliers (no integer division).
+struct PixDecode {
+    uint32_t rOW, rOH;
+    int sOW, sOH, OW, OH;
+    __device__ __forceinline__ explicit PixDecode(const Geo &g)
+        : rOW(g.rOW), rOH(g.rOH), sOW(recip_shift(g.OW)), sOH(recip_shift(g.OH)), OW(g.OW), OH(g.OH) {}
+    __device__ __forceinline__ void operator()(int m, int &n, int &oh, int &ow) const {
+        const int t = recip_div(m, rOW, sOW);
+        ow = m - t * OW;
+        n = recip_div(t, rOH, sOH);
+        oh = t - n * OH;
+    }
+};
 
 
 __device__ __forceinline__ void unpack_bf16x8(const uint4 &v, float (&f)[8]) {
@@ -103,6 +139,27 @@ constexpr int kBufFlags = 0x00020000;
 
 __device__ __forceinline__ __attribute__((address_space(3))) void *lds_ptr(uint8_t *p) {
     return (__attribute__((address_space(3))) void *)(p);
+}
+
+// 12 wait states (s_nop 7 + s_nop 3) behind the MFMAs that wrote one accumulator row, tied to the row through
+// its operands: whatever reads r afterwards, an asm statement included, reads settled registers.
+template <int TN>
+__device__ __forceinline__ void mfma_settle(f32x4 (&r)[TN]) {
+    static_assert(TN == 2 || TN == 4 || TN == 8, "one operand per accumulator block of the row");
+    if constexpr (TN == 2) asm volatile("s_nop 7\n\ts_nop 3" : "+v"(r[0]), "+v"(r[1]));
+    if constexpr (TN == 4) asm volatile("s_nop 7\n\ts_nop 3" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]));
+    if constexpr (TN == 8)
+        asm volatile("s_nop 7\n\ts_nop 3"
+                     : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7]));
+}
+
+// Minimum waves per SIMD asked of the register allocator for a conv_rows_kernel instance (1: the default).  The 8
+// waves of 32 x 64 (tile variant 25) run two workgroups per CU, four waves per SIMD, in their plain and
+// forward-statistics epilogues, which the allocator only keeps (126 VGPRs, no scratch) when told so; their
+// BN-backward epilogues need 138-140 VGPRs, three waves.
+template <int WM, int WN, int TM, int TN, int EPI>
+constexpr int rows_min_waves() {
+    return (WM * WN == 8 && TM * TN == 8 && (EPI & (kEpiBwdCoef | kEpiBwdBits)) == 0) ? 4 : 1;
 }
 
 // Tile and epilogue constants of one (waves, wave tile, epilogue) combination, shared by conv_kernel,
@@ -160,7 +217,15 @@ __device__ __forceinline__ void conv_store_tile(const f32x4 (&acc)[TM][TN], uint
             }
         }
 #pragma unroll
-    for (int i = 0; i < TM; ++i)
+    for (int i = 0; i < TM; ++i) {
+        // cvt_pk_bf16 is inline asm, and the compiler pads no hazard for an asm statement: reading an MFMA
+        // result needs 12 wait states after the 8-pass MFMA that wrote it.  mfma_settle supplies them for the
+        // accumulators of this row and hands them on as its outputs, so no conversion of the row can be
+        // scheduled above it and no MFMA of the row below it.
+        f32x4 a[TN];
+#pragma unroll
+        for (int j = 0; j < TN; ++j) a[j] = acc[i][j];
+        mfma_settle(a);
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             const int row = wm * WTM + i * 16 + (lane & 15);
@@ -168,17 +233,20 @@ __device__ __forceinline__ void conv_store_tile(const f32x4 (&acc)[TM][TN], uint
             float v4[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                float v = acc[i][j][r];
+                float v = a[j][r];
                 if constexpr (BIAS) v += bcol[j][r];
                 if constexpr ((EPI & kEpiBiasRelu) != 0) v = !(v <= 0.f) ? v : 0.f;  // NaN stays NaN (torch.relu)
                 v4[r] = v;
             }
-            // (integer rounding: v_cvt_pk_bf16_f32 here measured ResNet-50 20.24 -> 20.72 ms/step, the 56 x 56
-            // 3x3 conv 99 -> 163 us, r6t25 / profiles/r6_conv3x3_rows.md)
+            // hardware rounding through the asm helper, which keeps the accumulator registers as they are.
+            // (Round 6 tried the instruction here as __builtin_convertvector and measured the 56 x 56 3x3
+            // conv 99 -> 163 us: the builtin made the peeled last K-step write a second accumulator set,
+            // 96 AGPRs, and the row-image kernel fell to one wave per SIMD -- the instruction was not the
+            // cost, profiles/conv_epilogue_rounding.md.)
             *reinterpret_cast<uint2 *>(lds + row * CROW + col * 2) =
-                make_uint2(f32_to_bf16(v4[0]) | (static_cast<uint32_t>(f32_to_bf16(v4[1])) << 16),
-                           f32_to_bf16(v4[2]) | (static_cast<uint32_t>(f32_to_bf16(v4[3])) << 16));
+                make_uint2(cvt_pk_bf16(v4[0], v4[1]), cvt_pk_bf16(v4[2], v4[3]));
         }
+    }
     __syncthreads();
     // Store loop: thread -> 16-byte vectors (row, cv) with a FIXED 8-channel group cv (NT is a
     // multiple of VPR), so per-channel statistics accumulate in registers across its rows.
@@ -205,6 +273,7 @@ __device__ __forceinline__ void conv_store_tile(const f32x4 (&acc)[TM][TN], uint
             sh[k] = ea.fcoef[g.K + n0 + cv * 8 + k];
         }
     }
+    const PixDecode dec(g);
     for (int it0 = 0; it0 < ITER; it0 += U) {
         uint4 val[U], old[U], bxv[U];
         uint32_t amb[U], bmb[U];
@@ -218,8 +287,8 @@ __device__ __forceinline__ void conv_store_tile(const f32x4 (&acc)[TM][TN], uint
             ok[u] = m < g.M && col_ok;
             int pix = m;
             if (g.scat) {
-                const int t = m / g.OW, ow = m - t * g.OW;
-                const int n = t / g.OH, a = t - n * g.OH;
+                int n, a, ow;
+                dec(m, n, a, ow);
                 pix = (n * g.dh + 2 * a + g.pr) * g.dw + 2 * ow + g.pc;
             }
             const int64_t e = static_cast<int64_t>(pix) * g.K + n0 + cv * 8;
@@ -233,8 +302,9 @@ __device__ __forceinline__ void conv_store_tile(const f32x4 (&acc)[TM][TN], uint
                     bool here = true;
                     if constexpr ((EPI & kEpiAccEven) != 0) {
                         // only the even pixels hold a partial sum (a stride-2 1x1 data gradient)
-                        const int t = m / g.OW, ow = m - t * g.OW;
-                        here = ((ow | (t % g.OH)) & 1) == 0;
+                        int n, oh, ow;
+                        dec(m, n, oh, ow);
+                        here = ((ow | oh) & 1) == 0;
                     }
                     if (here) old[u] = *reinterpret_cast<const uint4 *>(y + e);
                     if constexpr ((EPI & kEpiAccMask) != 0) amb[u] = ea.amask[e >> 3];  // 8 channels, 8-aligned e
@@ -265,7 +335,7 @@ __device__ __forceinline__ void conv_store_tile(const f32x4 (&acc)[TM][TN], uint
                                      bf16_to_f32(static_cast<uint16_t>(b[k] & 0xffffu));
                     const float hi = bf16_to_f32(static_cast<uint16_t>(a[k] >> 16)) +
                                      bf16_to_f32(static_cast<uint16_t>(b[k] >> 16));
-                    o[k] = pack_bf16x2(lo, hi);
+                    o[k] = cvt_pk_bf16(lo, hi);
                 }
                 v = make_uint4(o[0], o[1], o[2], o[3]);
             }
@@ -296,7 +366,7 @@ __device__ __forceinline__ void conv_store_tile(const f32x4 (&acc)[TM][TN], uint
                         const float pdf = __expf(-0.5f * t * t) * 0.39894228040143268f;
                         d[h] = f[2 * k + h] * (cdf + t * pdf);
                     }
-                    vw[k] = pack_bf16x2(d[0], d[1]);
+                    vw[k] = cvt_pk_bf16(d[0], d[1]);
                 }
             }
             *reinterpret_cast<uint4 *>(y + ee[u]) = v;
@@ -380,7 +450,9 @@ __device__ __forceinline__ void conv_stats_flush(uint8_t *lds, const Geo &g, con
 // m-tiles mt0, mt0 + mstride, ... -- its per-channel statistics accumulate in registers
 // across all of them and reach the f64 slots with ONE set of atomics per block (instead of
 // one per tile: 3.2 M f64 atomics for a 56x56 64->256 conv at batch 256).
-template <int KS, int WM, int WN, int STAGES, int EPI, int TM = 4, int TN = 4, bool PERSIST = false>
+// FAST1 (KS = 1 only, conv_fast1(g) holds -- the launcher's choice): A row = m * C, no pixel decode.
+template <int KS, int WM, int WN, int STAGES, int EPI, int TM = 4, int TN = 4, bool PERSIST = false,
+          bool FAST1 = false>
 __global__ __launch_bounds__(64 * WM * WN) void conv_kernel(const uint16_t *__restrict__ x,
                                                             const uint16_t *__restrict__ w,
                                                             uint16_t *__restrict__ y, Geo g, EpiArgs ea) {
@@ -388,6 +460,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_kernel(const uint16_t *__re
     constexpr int WTM = T::WTM, WTN = T::WTN, BM = T::BM, BN = T::BN, NW = WM * WN;
     constexpr int KH = KS >= 16 ? (KS >> 4) : KS, KW = KS >= 16 ? (KS & 15) : KS;
     constexpr int TAPS = KH * KW;
+    static_assert(!FAST1 || KS == 1, "the decode-free A rows are a 1x1 path");
     constexpr int A_BYTES = BM * kRowBytes, B_BYTES = BN * kRowBytes;
     constexpr int STAGE = A_BYTES + B_BYTES;
     // A pieces (8 rows each): A_INST per wave; when BM / 8 is not a multiple of the wave count (the
@@ -416,6 +489,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_kernel(const uint16_t *__re
 #pragma unroll
     for (int k = 0; k < 8; ++k) s1[k] = s2[k] = 0.f;
     int mt_last = mt_first;
+    const PixDecode dec(g);
     for (int mt = mt_first; mt < g.mtiles; mt += mstride) {
     mt_last = mt;
     const int m0 = mt * BM;
@@ -437,8 +511,14 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_kernel(const uint16_t *__re
         const int m = m0 + r;
         a_off[j] = 0;
         a_ok[j] = 0;
-        if (m < g.M && piece < A_PIECES) {
-            const int ow = m % g.OW, t = m / g.OW, oh = t % g.OH, n = t / g.OH;
+        if constexpr (FAST1) {
+            if (m < g.M && piece < A_PIECES) {
+                a_off[j] = m * g.C + schunk * 8;
+                a_ok[j] = 1u;
+            }
+        } else if (m < g.M && piece < A_PIECES) {
+            int n, oh, ow;
+            dec(m, n, oh, ow);
             const int ih0 = oh * g.stride - g.ph, iw0 = ow * g.stride - g.pw;
             a_off[j] = ((n * g.H + ih0) * g.W + iw0) * g.C + schunk * 8;
             uint32_t ok = 0;
@@ -607,9 +687,8 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_kernel(const uint16_t *__re
 // fall from 9 (BM + BN) to about 1.1 BM + 9 BN rows per chunk.
 // The epilogue and the statistics flush are conv_kernel's (conv_store_tile / conv_stats_flush).
 template <int WM, int WN, int BST, int EPI, int TM, int TN, int IMG, int IMGB, bool PERSIST>
-__global__ __launch_bounds__(64 * WM * WN) void conv_rows_kernel(const uint16_t *__restrict__ x,
-                                                                 const uint16_t *__restrict__ w,
-                                                                 uint16_t *__restrict__ y, Geo g, EpiArgs ea) {
+__global__ __launch_bounds__(64 * WM * WN, (rows_min_waves<WM, WN, TM, TN, EPI>())) void conv_rows_kernel(
+    const uint16_t *__restrict__ x, const uint16_t *__restrict__ w, uint16_t *__restrict__ y, Geo g, EpiArgs ea) {
     using T = EpiTile<WM, WN, TM, TN, EPI>;
     constexpr int WTM = T::WTM, WTN = T::WTN, BM = T::BM, BN = T::BN, NW = WM * WN;
     constexpr int B_BYTES = BN * kRowBytes, IMG_BYTES = IMG * kRowBytes;
@@ -632,6 +711,8 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_rows_kernel(const uint16_t 
 #pragma unroll
     for (int k = 0; k < 8; ++k) s1[k] = s2[k] = 0.f;
     const int Wp = g.W + 2, HWp = (g.H + 2) * Wp;
+    const PixDecode dec(g);
+    const int sWp = recip_shift(Wp), sHp = recip_shift(g.H + 2);
     const int csteps = g.C / kBK;  // Cin % 64 == 0 (launcher)
     const int ksteps = 9 * csteps;
     const __amdgpu_buffer_rsrc_t xr =
@@ -647,10 +728,13 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_rows_kernel(const uint16_t 
         const int m0 = mt * BM;
         if (mt != mt_first) __syncthreads();
         auto gidx = [&](int m) {
-            const int ow = m % g.OW, t = m / g.OW, oh = t % g.OH, n = t / g.OH;
+            int n, oh, ow;
+            dec(m, n, oh, ow);
             return n * HWp + oh * Wp + ow;
         };
-        const int base = gidx(m0);
+        int n_b, oh_b, ow_b;  // the tile's first pixel: padded position (n_b, oh_b, ow_b) = slot 0
+        dec(m0, n_b, oh_b, ow_b);
+        const int base = n_b * HWp + oh_b * Wp + ow_b;
         const int mlast = (m0 + BM < g.M ? m0 + BM : g.M) - 1;
         const int nslots = gidx(mlast) - base + 2 * Wp + 3;
         // image staging: element offset of slot s's pixel (this lane's chunk), or -1 (zeros)
@@ -658,9 +742,11 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_rows_kernel(const uint16_t 
         // integer divisions per piece were ~1.5 k VALU instructions per wave and tile)
         int i_off[I_INST];
         {
+            // slot s0 is s0 padded columns past (n_b, oh_b, ow_b): carry columns into rows, rows into images
             const int s0 = wave * I_INST * 8 + srow;
-            int n = (base + s0) / HWp, r = base + s0 - n * HWp;
-            int ihp = r / Wp, iwp = r - ihp * Wp;
+            const int col = ow_b + s0, dr = recip_div(col, g.rWp, sWp);
+            const int row = oh_b + dr, dn = recip_div(row, g.rHp, sHp);
+            int n = n_b + dn, ihp = row - dn * (g.H + 2), iwp = col - dr * Wp;
 #pragma unroll
             for (int j = 0; j < I_INST; ++j) {
                 const int s = s0 + j * 8;
@@ -796,6 +882,7 @@ void launch_rows_epi(const uint16_t *x, const uint16_t *w, uint16_t *y, Geo g, c
     constexpr int BM = 16 * TM * WM, BN = 16 * TN * WN;
     g.mtiles = (g.M + BM - 1) / BM;
     g.ntiles = g.K / BN;
+    geo_recip(g);
     constexpr bool STATS = (EPI & (kEpiFwdStats | kEpiBwdCoef | kEpiBwdBits | kEpiGate)) != 0;
     if constexpr (STATS) {
         constexpr int LDS = IMGB * IMG * 128 + BST * BN * 128;
@@ -827,13 +914,15 @@ bool launch_rows_variant(const uint16_t *x, const uint16_t *w, uint16_t *y, Geo 
     }
 }
 
-template <int KS, int WM, int WN, int ST, int EPI, int TM = 4, int TN = 4>
+template <int KS, int WM, int WN, int ST, int EPI, int TM = 4, int TN = 4, bool FAST1 = false>
 void launch_epi(const uint16_t *x, const uint16_t *w, uint16_t *y, Geo g, const EpiArgs &ea, hipStream_t s) {
     constexpr int BM = 16 * TM * WM, BN = 16 * TN * WN;
     if (g.K % 8 || g.C % 8) throw std::invalid_argument("conv: Cin and Cout must be multiples of 8");
     check_buf_extent(g);
+    if (FAST1 && !conv_fast1(g)) throw std::invalid_argument("conv: not a decode-free 1x1 geometry");
     g.mtiles = (g.M + BM - 1) / BM;
     g.ntiles = (g.K + BN - 1) / BN;
+    geo_recip(g);
     constexpr bool STATS = (EPI & (kEpiFwdStats | kEpiBwdCoef | kEpiBwdBits | kEpiGate)) != 0;
     if constexpr (STATS) {
         // persistent blocks (4 per CU, fewer when the tile's LDS allows less): one atomic
@@ -844,37 +933,38 @@ void launch_epi(const uint16_t *x, const uint16_t *w, uint16_t *y, Geo g, const 
         const int cap = 256 * (OCC < 1 ? 1 : OCC);
         const int per_n = cap / g.ntiles;
         if (per_n >= 1 && g.mtiles > 2 * per_n) {
-            conv_kernel<KS, WM, WN, ST, EPI, TM, TN, true><<<per_n * g.ntiles, 64 * WM * WN, 0, s>>>(x, w, y, g, ea);
+            conv_kernel<KS, WM, WN, ST, EPI, TM, TN, true, FAST1><<<per_n * g.ntiles, 64 * WM * WN, 0, s>>>(x, w, y, g,
+                                                                                                       ea);
             return;
         }
     }
-    conv_kernel<KS, WM, WN, ST, EPI, TM, TN><<<g.mtiles * g.ntiles, 64 * WM * WN, 0, s>>>(x, w, y, g, ea);
+    conv_kernel<KS, WM, WN, ST, EPI, TM, TN, false, FAST1><<<g.mtiles * g.ntiles, 64 * WM * WN, 0, s>>>(x, w, y, g, ea);
 }
 
 // Every fused epilogue on one tile shape.
-template <int KS, int WM, int WN, int ST, int TM = 4, int TN = 4>
+template <int KS, int WM, int WN, int ST, int TM = 4, int TN = 4, bool FAST1 = false>
 void launch_variant(const uint16_t *x, const uint16_t *w, uint16_t *y, Geo g, const EpiArgs &ea, int epi,
                     hipStream_t s) {
     constexpr int A = kEpiAccum, M = kEpiAccMask, B = kEpiBwdBits, C = kEpiBwdCoef;
     switch (epi) {
-    case 0: launch_epi<KS, WM, WN, ST, 0, TM, TN>(x, w, y, g, ea, s); break;
-    case kEpiFwdStats: launch_epi<KS, WM, WN, ST, kEpiFwdStats, TM, TN>(x, w, y, g, ea, s); break;
-    case A: launch_epi<KS, WM, WN, ST, A, TM, TN>(x, w, y, g, ea, s); break;
-    case C: launch_epi<KS, WM, WN, ST, C, TM, TN>(x, w, y, g, ea, s); break;
-    case B: launch_epi<KS, WM, WN, ST, B, TM, TN>(x, w, y, g, ea, s); break;
-    case A | B: launch_epi<KS, WM, WN, ST, A | B, TM, TN>(x, w, y, g, ea, s); break;
-    case A | C: launch_epi<KS, WM, WN, ST, A | C, TM, TN>(x, w, y, g, ea, s); break;
-    case A | M: launch_epi<KS, WM, WN, ST, A | M, TM, TN>(x, w, y, g, ea, s); break;
-    case A | M | B: launch_epi<KS, WM, WN, ST, A | M | B, TM, TN>(x, w, y, g, ea, s); break;
-    case A | kEpiAccEven: launch_epi<KS, WM, WN, ST, A | kEpiAccEven, TM, TN>(x, w, y, g, ea, s); break;
-    case A | kEpiAccEven | B: launch_epi<KS, WM, WN, ST, A | kEpiAccEven | B, TM, TN>(x, w, y, g, ea, s); break;
-    case kEpiBiasRelu: launch_epi<KS, WM, WN, ST, kEpiBiasRelu, TM, TN>(x, w, y, g, ea, s); break;
-    case kEpiGate: launch_epi<KS, WM, WN, ST, kEpiGate, TM, TN>(x, w, y, g, ea, s); break;
+    case 0: launch_epi<KS, WM, WN, ST, 0, TM, TN, FAST1>(x, w, y, g, ea, s); break;
+    case kEpiFwdStats: launch_epi<KS, WM, WN, ST, kEpiFwdStats, TM, TN, FAST1>(x, w, y, g, ea, s); break;
+    case A: launch_epi<KS, WM, WN, ST, A, TM, TN, FAST1>(x, w, y, g, ea, s); break;
+    case C: launch_epi<KS, WM, WN, ST, C, TM, TN, FAST1>(x, w, y, g, ea, s); break;
+    case B: launch_epi<KS, WM, WN, ST, B, TM, TN, FAST1>(x, w, y, g, ea, s); break;
+    case A | B: launch_epi<KS, WM, WN, ST, A | B, TM, TN, FAST1>(x, w, y, g, ea, s); break;
+    case A | C: launch_epi<KS, WM, WN, ST, A | C, TM, TN, FAST1>(x, w, y, g, ea, s); break;
+    case A | M: launch_epi<KS, WM, WN, ST, A | M, TM, TN, FAST1>(x, w, y, g, ea, s); break;
+    case A | M | B: launch_epi<KS, WM, WN, ST, A | M | B, TM, TN, FAST1>(x, w, y, g, ea, s); break;
+    case A | kEpiAccEven: launch_epi<KS, WM, WN, ST, A | kEpiAccEven, TM, TN, FAST1>(x, w, y, g, ea, s); break;
+    case A | kEpiAccEven | B: launch_epi<KS, WM, WN, ST, A | kEpiAccEven | B, TM, TN, FAST1>(x, w, y, g, ea, s); break;
+    case kEpiBiasRelu: launch_epi<KS, WM, WN, ST, kEpiBiasRelu, TM, TN, FAST1>(x, w, y, g, ea, s); break;
+    case kEpiGate: launch_epi<KS, WM, WN, ST, kEpiGate, TM, TN, FAST1>(x, w, y, g, ea, s); break;
     default: throw std::invalid_argument("conv: unsupported epilogue combination");
     }
 }
 
-template <int KS>
+template <int KS, bool FAST1 = false>
 void launch_ks(const uint16_t *x, const uint16_t *w, uint16_t *y, Geo g, const EpiArgs &ea, int epi, hipStream_t s,
                int variant) {
     // default per shape (re-measured with the fused epilogues, tools/bench_conv1x1_variants.py
@@ -915,16 +1005,16 @@ void launch_ks(const uint16_t *x, const uint16_t *w, uint16_t *y, Geo g, const E
     // 256x256 of 128x64 waves, the 2- and 4-wave 64x128 -- never won a default, see
     // profiles/r3_conv_variants.txt, and are no longer instantiated)
     switch (variant) {
-    case 0: if (g.K % 128 == 0) { launch_variant<KS, 2, 2, 2>(x, w, y, g, ea, epi, s); break; }  // 128x128
+    case 0: if (g.K % 128 == 0) { launch_variant<KS, 2, 2, 2, 4, 4, FAST1>(x, w, y, g, ea, epi, s); break; }  // 128x128
             [[fallthrough]];
-    case 1: if (g.K % 128 == 0) { launch_variant<KS, 4, 2, 3>(x, w, y, g, ea, epi, s); break; }  // 256x128
+    case 1: if (g.K % 128 == 0) { launch_variant<KS, 4, 2, 3, 4, 4, FAST1>(x, w, y, g, ea, epi, s); break; }  // 256x128
             [[fallthrough]];
-    case 2: launch_variant<KS, 4, 1, 2>(x, w, y, g, ea, epi, s); break;                          // 256x64
+    case 2: launch_variant<KS, 4, 1, 2, 4, 4, FAST1>(x, w, y, g, ea, epi, s); break;                          // 256x64
     case 7: if (g.K % 256) throw std::invalid_argument("conv variant 7: Cout % 256");
-            launch_variant<KS, 4, 2, 2, 4, 8>(x, w, y, g, ea, epi, s); break;                  // 256x256, 8w, 64x128
+            launch_variant<KS, 4, 2, 2, 4, 8, FAST1>(x, w, y, g, ea, epi, s); break;                  // 256x256, 8w, 64x128
     case 8: if (g.K % 256) throw std::invalid_argument("conv variant 8: Cout % 256");
-            launch_variant<KS, 2, 4, 2, 7, 4>(x, w, y, g, ea, epi, s); break;                  // 224x256, 8w, 112x64
-    case 11: launch_variant<KS, 4, 1, 2, 4, 2>(x, w, y, g, ea, epi, s); break;                // 256x32 (Cout <= 32)
+            launch_variant<KS, 2, 4, 2, 7, 4, FAST1>(x, w, y, g, ea, epi, s); break;                  // 224x256, 8w, 112x64
+    case 11: launch_variant<KS, 4, 1, 2, 4, 2, FAST1>(x, w, y, g, ea, epi, s); break;                // 256x32 (Cout <= 32)
     default: throw std::invalid_argument("conv: tile variant must be -1, 0, 1, 2, 7, 8 or 11");
     }
 }

@@ -16,6 +16,7 @@ void launch_phase_t(const uint16_t *dy, const uint16_t *wt, uint16_t *dx, Geo g,
     if (g.K % 8 || g.C % 8) throw std::invalid_argument("conv_dgrad_s2: channel counts must be multiples of 8");
     g.mtiles = (g.M + BM - 1) / BM;
     g.ntiles = (g.K + BN - 1) / BN;  // a partial last N tile reads zero B rows, stores its valid columns
+    geo_recip(g);
     const int grid = g.mtiles * g.ntiles;
     check_buf_extent(g);
     if (epi == 0) conv_kernel<KS, WM, WN, ST, 0, TM, TN><<<grid, 64 * WM * WN, 0, s>>>(dy, wt, dx, g, ea);
