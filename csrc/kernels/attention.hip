@@ -103,7 +103,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
                 const float v = acc[j][i][r] * inv;
                 p[r] = keep_elem(seed, bh, row, kb0 + r, a.thresh) ? v * a.inv_keep : 0.f;
             }
-            *reinterpret_cast<uint2 *>(Pi + off<PROW>(row, kb0)) = make_uint2(pack2(p[0], p[1]), pack2(p[2], p[3]));
+            *reinterpret_cast<uint2 *>(Pi + off<PROW>(row, kb0)) = make_uint2(pack_bf16x2_hw(p[0], p[1]),
+                                                                              pack_bf16x2_hw(p[2], p[3]));
         }
     }
     __syncthreads();
@@ -131,7 +132,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
         for (int i = 0; i < TQ; ++i) {
             const int q = q0 + 16 * i + lc;
             uint16_t *dst = a.out + (static_cast<int64_t>(b) * S + q) * D + h * DH + 16 * c + 4 * lg;
-            *reinterpret_cast<uint2 *>(dst) = make_uint2(pack2(o[c][i][0], o[c][i][1]), pack2(o[c][i][2], o[c][i][3]));
+            *reinterpret_cast<uint2 *>(dst) = make_uint2(pack_bf16x2_hw(o[c][i][0], o[c][i][1]),
+                                                         pack_bf16x2_hw(o[c][i][2], o[c][i][3]));
         }
 }
 
@@ -231,8 +233,10 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_kernel(AttnArgs a) {
                 pv[r] = kp ? p * a.inv_keep : 0.f;
                 sv[r] = p * (dpd - dd);
             }
-            *reinterpret_cast<uint2 *>(Pi + off<PROW>(row, kb0)) = make_uint2(pack2(pv[0], pv[1]), pack2(pv[2], pv[3]));
-            *reinterpret_cast<uint2 *>(Si + off<PROW>(row, kb0)) = make_uint2(pack2(sv[0], sv[1]), pack2(sv[2], sv[3]));
+            *reinterpret_cast<uint2 *>(Pi + off<PROW>(row, kb0)) = make_uint2(pack_bf16x2_hw(pv[0], pv[1]),
+                                                                              pack_bf16x2_hw(pv[2], pv[3]));
+            *reinterpret_cast<uint2 *>(Si + off<PROW>(row, kb0)) = make_uint2(pack_bf16x2_hw(sv[0], sv[1]),
+                                                                              pack_bf16x2_hw(sv[2], sv[3]));
         }
     }
     __syncthreads();
@@ -261,8 +265,9 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_kernel(AttnArgs a) {
             for (int c = 0; c < 4; ++c) {
                 const int q = q0 + 16 * i + lc;
                 uint16_t *dst = a.dqkv + (static_cast<int64_t>(b) * S + q) * RS + h * DH + 16 * c + 4 * lg;
-                *reinterpret_cast<uint2 *>(dst) = make_uint2(pack2(o[c][i][0] * a.scale, o[c][i][1] * a.scale),
-                                                             pack2(o[c][i][2] * a.scale, o[c][i][3] * a.scale));
+                *reinterpret_cast<uint2 *>(dst) =
+                    make_uint2(pack_bf16x2_hw(o[c][i][0] * a.scale, o[c][i][1] * a.scale),
+                               pack_bf16x2_hw(o[c][i][2] * a.scale, o[c][i][3] * a.scale));
             }
     }
     // ---- phase 2: key rows k0 .. k0 + QW - 1
@@ -299,10 +304,11 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_kernel(AttnArgs a) {
         for (int c = 0; c < 4; ++c) {
             const int key = k0 + 16 * j + lc;
             uint16_t *row = a.dqkv + (static_cast<int64_t>(b) * S + key) * RS + h * DH + 16 * c + 4 * lg;
-            *reinterpret_cast<uint2 *>(row + D) = make_uint2(pack2(dk[c][j][0] * a.scale, dk[c][j][1] * a.scale),
-                                                             pack2(dk[c][j][2] * a.scale, dk[c][j][3] * a.scale));
+            *reinterpret_cast<uint2 *>(row + D) =
+                make_uint2(pack_bf16x2_hw(dk[c][j][0] * a.scale, dk[c][j][1] * a.scale),
+                           pack_bf16x2_hw(dk[c][j][2] * a.scale, dk[c][j][3] * a.scale));
             *reinterpret_cast<uint2 *>(row + 2 * D) =
-                make_uint2(pack2(dv[c][j][0], dv[c][j][1]), pack2(dv[c][j][2], dv[c][j][3]));
+                make_uint2(pack_bf16x2_hw(dv[c][j][0], dv[c][j][1]), pack_bf16x2_hw(dv[c][j][2], dv[c][j][3]));
         }
 }
 

@@ -5,30 +5,18 @@
 #pragma once
 #include "common.hpp"
 #include "kernels.hpp"
+#include "mfma_util.hpp"
 
 namespace kfk {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
 constexpr int DH = 64;  // head dim
 
-// swizzle of the 32-byte column group by the row: 128-byte rows (64 bf16) / 256-byte rows
-template <int ROW>
-__device__ __forceinline__ int hsw(int row) {
-    if constexpr (ROW == 256) return (row & 3) | (((row >> 3) & 1) << 2);
-    else return ((row >> 1) & 1) | (((row >> 3) & 1) << 1);
-}
+// byte offset of bf16 (row, col) in an image of ROW-byte rows (128: 64 bf16, or 256), swizzled by hswz
 template <int ROW>
 __device__ __forceinline__ int off(int row, int col) {
-    return row * ROW + (((col >> 4) ^ hsw<ROW>(row)) << 5) + (col & 15) * 2;
+    return row * ROW + (((col >> 4) ^ hswz<ROW>(row)) << 5) + (col & 15) * 2;
 }
 
 __device__ __forceinline__ bf16x8 rd128(const uint8_t *p) { return *reinterpret_cast<const bf16x8 *>(p); }
@@ -39,6 +27,8 @@ template <int ROW>
 __device__ __forceinline__ bf16x8 tr_frag(const uint8_t *img, int k0, int c0, int lane) {
     const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
     const int r = k0 + 8 * g + q, c = c0 + 4 * p;
+    // (not through the pointer-pair tr_frag: forming both addresses before the first read reorders
+    // these kernels' LDS reads)
     const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(img + off<ROW>(r, c)));
     const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(img + off<ROW>(r + 4, c)));
     return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
@@ -52,10 +42,6 @@ __device__ __forceinline__ bf16x8 row_frag(const uint8_t *img, int r0, int k0, i
 
 __device__ __forceinline__ f32x4 mfma(const bf16x8 &a, const bf16x8 &b, const f32x4 &c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2{a, b}), bf16x2));
 }
 
 // Dropout keep test: a counter hash of (seed, sequence*heads + head, query, key).  The same
@@ -72,11 +58,6 @@ __device__ __forceinline__ bool keep_elem(uint32_t seed, uint32_t bh, uint32_t q
     return x >= thresh;
 }
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // Stage NIMG images of S rows x 64 bf16 (128-byte rows) with 16-byte global_load_lds: image t
 // row r comes from src[t] + r * stride[t]; the NW waves split the 1 KB (8-row) pieces.
 template <int S, int NIMG, int NW = 4>
@@ -90,7 +71,7 @@ __device__ __forceinline__ void stage_images(uint8_t *lds, const uint16_t *const
         const int gp = wave + NW * u;
         const int t = gp / PIECES, pc = gp - t * PIECES;
         const int r = pc * 8 + (lane >> 3);
-        const int col = ((((pch >> 1) ^ hsw<128>(r)) << 1) | (pch & 1)) * 8;
+        const int col = ((((pch >> 1) ^ hswz<128>(r)) << 1) | (pch & 1)) * 8;
         const uint16_t *s = src[t] + static_cast<int64_t>(r) * stride[t] + col;
         __builtin_amdgcn_global_load_lds(s, lds + t * S * 128 + pc * 1024, 16, 0, 0);
     }

@@ -128,7 +128,8 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(AttnArgs a, int S) {
                     sum += e;
                     p[r] = keep_elem(seed, bh, row, kb * BK + kb0 + r, a.thresh) ? e * a.inv_keep : 0.f;
                 }
-                *reinterpret_cast<uint2 *>(Pi + off<128>(lrow, kb0)) = make_uint2(pack2(p[0], p[1]), pack2(p[2], p[3]));
+                *reinterpret_cast<uint2 *>(Pi + off<128>(lrow, kb0)) = make_uint2(pack_bf16x2_hw(p[0], p[1]),
+                                                                                  pack_bf16x2_hw(p[2], p[3]));
             }
             sum += __shfl_xor(sum, 16);
             sum += __shfl_xor(sum, 32);
@@ -162,7 +163,8 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(AttnArgs a, int S) {
         for (int c = 0; c < 4; ++c) {
             uint16_t *dst = a.out + (static_cast<int64_t>(b) * S + q) * D + h * DH + 16 * c + 4 * lg;
             *reinterpret_cast<uint2 *>(dst) =
-                make_uint2(pack2(o[c][i][0] * inv, o[c][i][1] * inv), pack2(o[c][i][2] * inv, o[c][i][3] * inv));
+                make_uint2(pack_bf16x2_hw(o[c][i][0] * inv, o[c][i][1] * inv),
+                           pack_bf16x2_hw(o[c][i][2] * inv, o[c][i][3] * inv));
         }
     }
 }
@@ -232,8 +234,10 @@ __device__ __forceinline__ void bwd_block_scores(const AttnArgs &a, uint32_t see
             sv[r] = p * (dpd - dd);
         }
         if (Pi)
-            *reinterpret_cast<uint2 *>(Pi + off<128>(qw0 + lc, kb0)) = make_uint2(pack2(pv[0], pv[1]), pack2(pv[2], pv[3]));
-        *reinterpret_cast<uint2 *>(Si + off<128>(qw0 + lc, kb0)) = make_uint2(pack2(sv[0], sv[1]), pack2(sv[2], sv[3]));
+            *reinterpret_cast<uint2 *>(Pi + off<128>(qw0 + lc, kb0)) = make_uint2(pack_bf16x2_hw(pv[0], pv[1]),
+                                                                                  pack_bf16x2_hw(pv[2], pv[3]));
+        *reinterpret_cast<uint2 *>(Si + off<128>(qw0 + lc, kb0)) = make_uint2(pack_bf16x2_hw(sv[0], sv[1]),
+                                                                              pack_bf16x2_hw(sv[2], sv[3]));
     }
 }
 
@@ -301,7 +305,8 @@ __global__ __launch_bounds__(256) void attn_long_dq_kernel(AttnArgs a, float *ds
     for (int c = 0; c < 4; ++c) {
         uint16_t *dst = a.dqkv + (static_cast<int64_t>(b) * S + row) * RS + h * DH + 16 * c + 4 * lg;
         *reinterpret_cast<uint2 *>(dst) =
-            make_uint2(pack2(o[c][0] * a.scale, o[c][1] * a.scale), pack2(o[c][2] * a.scale, o[c][3] * a.scale));
+            make_uint2(pack_bf16x2_hw(o[c][0] * a.scale, o[c][1] * a.scale),
+                       pack_bf16x2_hw(o[c][2] * a.scale, o[c][3] * a.scale));
     }
 }
 
@@ -367,8 +372,10 @@ __global__ __launch_bounds__(256) void attn_long_dkv_kernel(AttnArgs a, const fl
     for (int c = 0; c < 4; ++c) {
         uint16_t *rowp = a.dqkv + (static_cast<int64_t>(b) * S + key) * RS + h * DH + 16 * c + 4 * lg;
         *reinterpret_cast<uint2 *>(rowp + D) =
-            make_uint2(pack2(dk[c][0] * a.scale, dk[c][1] * a.scale), pack2(dk[c][2] * a.scale, dk[c][3] * a.scale));
-        *reinterpret_cast<uint2 *>(rowp + 2 * D) = make_uint2(pack2(dv[c][0], dv[c][1]), pack2(dv[c][2], dv[c][3]));
+            make_uint2(pack_bf16x2_hw(dk[c][0] * a.scale, dk[c][1] * a.scale),
+                       pack_bf16x2_hw(dk[c][2] * a.scale, dk[c][3] * a.scale));
+        *reinterpret_cast<uint2 *>(rowp + 2 * D) = make_uint2(pack_bf16x2_hw(dv[c][0], dv[c][1]),
+                                                              pack_bf16x2_hw(dv[c][2], dv[c][3]));
     }
 }
 

@@ -34,23 +34,6 @@ namespace kfk {
 
 namespace {
 
-__device__ __forceinline__ void unpack8v(const uint4 &v, float (&f)[8]) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = __uint_as_float(w[i] << 16);
-        f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-}
-
-__device__ __forceinline__ uint4 pack8v(const float (&f)[8]) {
-    uint32_t w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        w[i] = pack_bf16x2(f[2 * i], f[2 * i + 1]);
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
 template <int CVEC, bool RELU>
 __global__ __launch_bounds__(kBlock) void bias_act_fwd_kernel(uint4 *__restrict__ y, const float *__restrict__ bias,
                                                               int64_t nvec) {
@@ -62,13 +45,13 @@ __global__ __launch_bounds__(kBlock) void bias_act_fwd_kernel(uint4 *__restrict_
     const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
     for (int64_t i = tid; i < nvec; i += stride) {
         float f[8];
-        unpack8v(y[i], f);
+        unpack_bf16x8(y[i], f);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             f[k] += b[k];
             if (RELU) f[k] = !(f[k] <= 0.f) ? f[k] : 0.f;  // NaN stays NaN (torch.relu)
         }
-        y[i] = pack8v(f);
+        y[i] = pack_bf16x8(f);
     }
 }
 
@@ -86,13 +69,13 @@ __global__ __launch_bounds__(kBlock) void bias_act_bwd_kernel(const uint4 *__res
     const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
     for (int64_t i = tid; i < nvec; i += stride) {
         float g[8];
-        unpack8v(dy[i], g);
+        unpack_bf16x8(dy[i], g);
         if (RELU) {
             float v[8];
-            unpack8v(y[i], v);
+            unpack_bf16x8(y[i], v);
 #pragma unroll
             for (int k = 0; k < 8; ++k) g[k] = v[k] > 0.f ? g[k] : 0.f;
-            dz[i] = pack8v(g);
+            dz[i] = pack_bf16x8(g);
         }
 #pragma unroll
         for (int k = 0; k < 8; ++k) acc[k] += g[k];

@@ -38,23 +38,6 @@ namespace kfk {
 
 namespace {
 
-__device__ __forceinline__ void unpack8(const uint4 &v, float (&f)[8]) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = __uint_as_float(w[i] << 16);
-        f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-}
-
-__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
-    uint32_t w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        w[i] = pack_bf16x2(f[2 * i], f[2 * i + 1]);
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
 // Non-temporal 16-byte accesses (bn_nt_mode(): bit 0 loads, bit 1 stores), for the apply passes
 // that stream every byte exactly once.  A uniform runtime flag: both paths are in one kernel.
 typedef unsigned int kf_u32x4 __attribute__((ext_vector_type(4)));
@@ -204,7 +187,7 @@ __global__ __launch_bounds__(kBlock) void bn_stats_kernel(const uint4 *__restric
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             float f[8];
-            unpack8(v[u], f);
+            unpack_bf16x8(v[u], f);
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 acc[0][k] += f[k];
@@ -214,7 +197,7 @@ __global__ __launch_bounds__(kBlock) void bn_stats_kernel(const uint4 *__restric
     }
     for (; r < r_end; r += RPI) {
         float f[8];
-        unpack8(x[r * CVEC + cv], f);
+        unpack_bf16x8(x[r * CVEC + cv], f);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             acc[0][k] += f[k];
@@ -424,9 +407,9 @@ __global__ __launch_bounds__(kBlock) void bn_apply_kernel(const uint4 *__restric
             const int64_t i = i0 + u * stride;
             if (i >= nvec) break;
             float f[8];
-            unpack8(xr[u], f);
+            unpack_bf16x8(xr[u], f);
             float rr[8];
-            if (RES) unpack8(rr4[u], rr);
+            if (RES) unpack_bf16x8(rr4[u], rr);
             uint32_t m = 0;
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
@@ -439,8 +422,8 @@ __global__ __launch_bounds__(kBlock) void bn_apply_kernel(const uint4 *__restric
                 }
                 f[k] = v;
             }
-            if constexpr (SOUT) st16(y + (i / CVEC) * y_ldv + cv, pack8(f), nts);
-            else st16(y + i, pack8(f), nts);
+            if constexpr (SOUT) st16(y + (i / CVEC) * y_ldv + cv, pack_bf16x8(f), nts);
+            else st16(y + i, pack_bf16x8(f), nts);
             if (RES && RELU) mask[i] = static_cast<uint8_t>(m);
         }
     }
@@ -491,7 +474,7 @@ __global__ __launch_bounds__(kBlock) void bn_pool_apply_kernel(const uint4 *__re
                 const int w = 2 * ow - 1 + kw;
                 if (w < 0 || w >= W) continue;
                 float f[8];
-                unpack8(x[((n * H + h) * W + w) * CVEC + cv], f);
+                unpack_bf16x8(x[((n * H + h) * W + w) * CVEC + cv], f);
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
                     float v = f[k] * sc[k] + sh[k];
@@ -504,10 +487,10 @@ __global__ __launch_bounds__(kBlock) void bn_pool_apply_kernel(const uint4 *__re
                 }
             }
         }
-        yp[i] = pack8(best);
+        yp[i] = pack_bf16x8(best);
         arg[i] = make_uint2(a[0] | (a[1] << 8) | (a[2] << 16) | (a[3] << 24),
                             a[4] | (a[5] << 8) | (a[6] << 16) | (a[7] << 24));
-        if (xarg) xarg[i] = pack8(xb);  // exact: bf16 inputs re-packed
+        if (xarg) xarg[i] = pack_bf16x8(xb);  // exact: bf16 inputs re-packed
     }
 }
 
@@ -534,8 +517,8 @@ __global__ __launch_bounds__(kBlock) void bn_pool_bwd_sums_kernel(const uint4 *_
     const int64_t stride = static_cast<int64_t>(gridDim.x) * NT;
     for (int64_t i = tid; i < nvec; i += stride) {
         float g[8], xv[8];
-        unpack8(dy[i], g);
-        unpack8(xarg[i], xv);
+        unpack_bf16x8(dy[i], g);
+        unpack_bf16x8(xarg[i], xv);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const float dz = xv[k] * sc[k] + sh[k] > 0.f ? g[k] : 0.f;
@@ -578,7 +561,7 @@ struct DirectGrad {
     __device__ __forceinline__ Raw fetch(int64_t i, int64_t /*row*/, int /*cv*/) const {
         return ld16(dy + i, nt);
     }
-    __device__ __forceinline__ void get(const Raw &r, float (&g)[8]) const { unpack8(r, g); }
+    __device__ __forceinline__ void get(const Raw &r, float (&g)[8]) const { unpack_bf16x8(r, g); }
 };
 
 // dy is a channel slice of a wider channels-last tensor (row stride ldv 16-byte vectors): the
@@ -591,7 +574,7 @@ struct StridedGrad {
     __device__ __forceinline__ Raw fetch(int64_t /*i*/, int64_t row, int cv) const {
         return dy[row * ldv + cv];
     }
-    __device__ __forceinline__ void get(const Raw &r, float (&g)[8]) const { unpack8(r, g); }
+    __device__ __forceinline__ void get(const Raw &r, float (&g)[8]) const { unpack_bf16x8(r, g); }
 };
 
 // dy of the BN output gathered from the max-pool gradient: input pixel (h, w)
@@ -617,7 +600,7 @@ struct PoolGrad {
         for (int c = 0; c < 4; ++c) {
             const uint32_t kk = (r.kk >> (8 * c)) & 0xffu;
             float d[8];
-            unpack8(r.d[c], d);
+            unpack_bf16x8(r.d[c], d);
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const uint32_t ak = ((k < 4 ? r.am[c].x : r.am[c].y) >> (8 * (k & 3))) & 0xffu;
@@ -722,7 +705,7 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_reduce_kernel(G grad, const uin
         for (int u = 0; u < U; ++u) {
             float g[8], xv[8];
             grad.get(gr[u], g);
-            unpack8(xr[u], xv);
+            unpack_bf16x8(xr[u], xv);
             relu_gate<RM>(g, xv, sc, sh, mask, (r + u * RPI) * CVEC + cv);
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
@@ -735,7 +718,7 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_reduce_kernel(G grad, const uin
         const int64_t i = r * CVEC + cv;
         float g[8], xv[8];
         grad.get(grad.template fetch<CVEC>(i, r, cv), g);
-        unpack8(x[i], xv);
+        unpack_bf16x8(x[i], xv);
         relu_gate<RM>(g, xv, sc, sh, mask, i);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
@@ -795,15 +778,15 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_apply_kernel(G grad, const uint
             if (i >= nvec) break;
             float g[8], xv[8];
             grad.get(gr[u], g);
-            unpack8(xr[u], xv);
+            unpack_bf16x8(xr[u], xv);
             relu_gate<RM>(g, xv, sc, sh, mask, i);
             if (DRES) {
-                const uint4 gr = pack8(g);
+                const uint4 gr = pack_bf16x8(g);
                 st16(dres + i, gr, nts);
                 if (dsum) {
                     float gq[8], sx[8];
-                    unpack8(gr, gq);
-                    unpack8(dsx[i], sx);
+                    unpack_bf16x8(gr, gq);
+                    unpack_bf16x8(dsx[i], sx);
 #pragma unroll
                     for (int k = 0; k < 8; ++k) {
                         d1[k] += gq[k];
@@ -814,7 +797,7 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_apply_kernel(G grad, const uint
             float o[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) o[k] = k1[k] * g[k] + k2[k] * xv[k] + k3[k];
-            st16(dx + i, pack8(o), nts);
+            st16(dx + i, pack_bf16x8(o), nts);
         }
     }
     if (dsum) {

@@ -41,7 +41,16 @@ inline int grid_for(size_t n_vec) {
 }
 
 __device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float(static_cast<uint32_t>(h) << 16); }
+// the two bf16 halves of a 32-bit word as f32
+__device__ __forceinline__ float bf16_lo(uint32_t w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float bf16_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
 
+// f32 pair -> bf16 pair comes in THREE forms that give the same bits for finite inputs and differ in
+// what the compiler makes of the code around them: pack_bf16x2 (integer arithmetic), cvt_pk_bf16
+// (v_cvt_pk_bf16_f32 through inline asm) and pack_bf16x2_hw (the same instruction through
+// __builtin_convertvector).  Which one a call site uses is measured per kernel; a helper that moves
+// between files keeps the form it had.
+//
 // f32 -> bf16, round to nearest even, in integer arithmetic (about 2.5 vector instructions per
 // value).  Finite inputs and infinities only: a NaN is NOT guaranteed to stay one (0x7f800001
 // rounds to +inf, 0x7fffffff carries into the sign and gives -0).  gfx950's v_cvt_pk_bf16_f32 gives
@@ -71,6 +80,51 @@ __device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) {
     uint32_t r;
     asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
     return r;
+}
+// The same instruction as a builtin conversion, schedulable like any other op.  Used where it measured
+// faster than the integer form: the stem forward epilogue and the stem weight gradient's dx, stem3's
+// im2col packing and the attention kernels' P / dS / output packs (r6t15: ResNet-50 20.24-20.27 vs
+// 20.35-20.42 ms/step with attention / stem / stem3 on it).  In gemm.hip's epilogues the same builtin
+// measured 6.5x slower (r6t14, the scratch described at f32_to_bf16), so it is never the default.
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+__device__ __forceinline__ uint32_t pack_bf16x2_hw(float lo, float hi) {
+    const bf16x2 v = __builtin_convertvector(f32x2{lo, hi}, bf16x2);
+    return __builtin_bit_cast(uint32_t, v);
+}
+
+// 8 (16 bytes) or 4 (8 bytes) bf16 <-> f32; the packs round with pack_bf16x2 (the integer form)
+__device__ __forceinline__ void unpack_bf16x8(const uint4 &v, float (&f)[8]) {
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        f[2 * i] = bf16_lo(w[i]);
+        f[2 * i + 1] = bf16_hi(w[i]);
+    }
+}
+__device__ __forceinline__ uint4 pack_bf16x8(const float (&f)[8]) {
+    uint32_t w[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) w[i] = pack_bf16x2(f[2 * i], f[2 * i + 1]);
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+// acc += the 8 bf16 of v
+__device__ __forceinline__ void add_bf16x8(const uint4 &v, float (&acc)[8]) {
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        acc[2 * i] += bf16_lo(w[i]);
+        acc[2 * i + 1] += bf16_hi(w[i]);
+    }
+}
+__device__ __forceinline__ void unpack_bf16x4(const uint2 &v, float (&f)[4]) {
+    f[0] = bf16_lo(v.x);
+    f[1] = bf16_hi(v.x);
+    f[2] = bf16_lo(v.y);
+    f[3] = bf16_hi(v.y);
+}
+__device__ __forceinline__ uint2 pack_bf16x4(const float (&f)[4]) {
+    return make_uint2(pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]));
 }
 
 __device__ __forceinline__ float f16_to_f32(uint16_t h) {

@@ -31,6 +31,7 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "mfma_util.hpp"
 #include "recip_div.hpp"
 
 #include <cstdlib>
@@ -88,9 +89,6 @@ void launch_conv_k1_fast(const uint16_t *x, const uint16_t *w, uint16_t *y, Geo 
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
 __device__ __forceinline__ int wm_of(int wave, int wn) { return wave / wn; }
 
 // Output pixel m -> (n, oh, ow) with the launch's reciprocal multipliers (no integer division).
@@ -107,16 +105,6 @@ struct PixDecode {
     }
 };
 
-
-__device__ __forceinline__ void unpack_bf16x8(const uint4 &v, float (&f)[8]) {
-    const uint32_t *u = reinterpret_cast<const uint32_t *>(&v);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        f[2 * k] = __uint_as_float(u[k] << 16);
-        f[2 * k + 1] = __uint_as_float(u[k] & 0xffff0000u);
-    }
-}
-
 constexpr int kBK = 64;              // channels per K-step
 constexpr int kRowBytes = kBK * 2;   // 128 B per staged row
 
@@ -125,21 +113,10 @@ __device__ __forceinline__ int swz_chunk(int row, int chunk) { return chunk ^ (r
 // LDS byte address of (row, 16-B chunk) in a staged tile image.
 __device__ __forceinline__ int img_off(int row, int chunk) { return row * kRowBytes + (swz_chunk(row, chunk) << 4); }
 
-
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // Buffer-resource LDS-DMA staging in conv_kernel / conv_rows_kernel: num_records = 2 GiB, so
 // the out-of-range offset kBufOOB returns zeros; dword 3 = the CDNA raw-buffer format word.
 constexpr uint32_t kBufOOB = 0x80000000u;
 constexpr int kBufFlags = 0x00020000;
-
-__device__ __forceinline__ __attribute__((address_space(3))) void *lds_ptr(uint8_t *p) {
-    return (__attribute__((address_space(3))) void *)(p);
-}
 
 // 12 wait states (s_nop 7 + s_nop 3) behind the MFMAs that wrote one accumulator row, tied to the row through
 // its operands: whatever reads r afterwards, an asm statement included, reads settled registers.
@@ -478,10 +455,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_kernel(const uint16_t *__re
     __shared__ __attribute__((aligned(1024))) uint8_t lds[LDS_BYTES];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // XCD-aware bijective remap: blocks sharing an XCD get consecutive tile ids.
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    const int q = nwg >> 3, rr = nwg & 7, xcd = orig & 7;
-    const int wg = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (orig >> 3);
+    const int nwg = gridDim.x, wg = xcd_remap(blockIdx.x, nwg);
     const int mt_first = wg / g.ntiles, nt = wg - mt_first * g.ntiles;
     const int n0 = nt * BN;
     const int mstride = PERSIST ? nwg / g.ntiles : g.mtiles;  // nwg % ntiles == 0 when persistent
@@ -701,9 +675,7 @@ __global__ __launch_bounds__(64 * WM * WN, (rows_min_waves<WM, WN, TM, TN, EPI>(
     __shared__ __attribute__((aligned(1024))) uint8_t lds[LDS_BYTES];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    const int q = nwg >> 3, rr = nwg & 7, xcd = orig & 7;
-    const int wg = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (orig >> 3);
+    const int nwg = gridDim.x, wg = xcd_remap(blockIdx.x, nwg);
     const int mt_first = wg / g.ntiles, nt = wg - mt_first * g.ntiles;
     const int n0 = nt * BN;
     const int mstride = PERSIST ? nwg / g.ntiles : g.mtiles;

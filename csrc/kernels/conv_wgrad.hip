@@ -13,7 +13,7 @@
 // pixels of one channel -- no register/ds_write transpose pass.
 //
 // LDS image: rows of 128 or 256 bytes (64 / 128 channels), 32-byte column groups
-// XOR-swizzled by the row (h(row) below) so the 8 rows one 32-lane half of a
+// XOR-swizzled by the row (hswz, mfma_util.hpp) so the 8 rows one 32-lane half of a
 // transposing read touches (two 4-row blocks 8 rows apart) land on 8 distinct
 // 32-byte bank groups: conflict-free.  The swizzle is applied on the staging source
 // address (global_load_lds writes fixed LDS offsets) and on the read address.
@@ -35,6 +35,7 @@
 // RRGeo) that planner fills, and the one launcher that runs a plan.
 #include "common.hpp"
 #include "kernels.hpp"
+#include "mfma_util.hpp"
 
 #include <stdexcept>
 
@@ -44,43 +45,12 @@ const void *zero_page();  // conv.hip
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
 constexpr int kBK = 64;  // pixels per K-step
 
 // Cache policy of the split-K kernel's LDS-DMA operand loads: non-temporal (aux = 2).  Measured
 // on the ResNet-50 step (r3h, tools/gpu_r3_ntconv.sh): +1 % with nt on both operands; the same
 // hint on the forward / data-gradient conv kernel's activation loads cost 1.5-2 %.
 constexpr int kWgradAux = 2;
-
-__device__ __forceinline__ int fdiv(int p, uint64_t m) {
-    return static_cast<int>((static_cast<uint64_t>(static_cast<uint32_t>(p)) * m) >> 40);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// 32-byte column-group swizzle of an LDS image row (ROW = 128, 256 or 512 bytes; a 512-byte
-// row spans two 256-byte bank cycles, so the 3-bit swizzle of 256-byte rows serves it too).
-template <int ROW>
-__device__ __forceinline__ int hswz(int row) {
-    if constexpr (ROW >= 256) return (row & 3) | (((row >> 3) & 1) << 2);
-    else if constexpr (ROW == 64) return (row >> 3) & 1;  // 4 rows per 256-byte bank cycle: flip rows 8..15
-    else return ((row >> 1) & 1) | (((row >> 3) & 1) << 1);
-}
-
-__device__ __forceinline__ bf16x8 tr_frag(const uint8_t *p0, const uint8_t *p1) {
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(p0));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(p1));
-    const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8, v);
-}
 
 // WM x WN waves (wave tile 64 co x 16*TN ci), STAGES-deep global_load_lds ring; S = stride.
 // KS = 1 | 3 (pad (KS-1)/2), or 0: a KH x KW window with padding (g.kwin, g.ph, g.pw) at run
@@ -95,7 +65,7 @@ __global__ __launch_bounds__(64 * WM * WN) void wgrad_kernel(const uint16_t *__r
                                                              float *__restrict__ part, void *__restrict__ dw,
                                                              const uint16_t *__restrict__ zero, WGeo g,
                                                              int out_f32, int accumulate, int atomic_out,
-                                                             int stagger = 0) {
+                                                             int stagger) {
     constexpr int BM = 64 * WM, BN = 16 * TN * WN, NW = WM * WN, NT = 64 * NW;
     constexpr int PAD = KS > 0 ? (KS - 1) / 2 : 0;
     constexpr int ROWA = BM * 2, ROWB = BN * 2;  // bytes per staged pixel row
@@ -110,9 +80,7 @@ __global__ __launch_bounds__(64 * WM * WN) void wgrad_kernel(const uint16_t *__r
     __shared__ __attribute__((aligned(1024))) uint8_t lds[STAGES * STAGE];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    const int q8 = nwg >> 3, rr = nwg & 7, xcd = orig & 7;
-    const int wg = (xcd < rr ? xcd * (q8 + 1) : rr * (q8 + 1) + (xcd - rr) * q8) + (orig >> 3);
+    const int wg = xcd_remap(blockIdx.x, gridDim.x);
     const int split = wg / g.tiles, tile = wg - split * g.tiles;
     const int mn = g.mtiles * g.ntiles;
     const int tap = tile / mn, rem = tile - tap * mn;
@@ -327,12 +295,12 @@ __global__ __launch_bounds__(64 * WM * WN) void wgrad_kernel(const uint16_t *__r
 //     is only an address offset -- every input pixel is staged once per segment.
 // 33-35 LDS-DMA pieces per K-step are spread over the 9 waves (4 each) against 32 MFMAs per
 // wave.  Partial tiles use wgrad_kernel's workspace order (reduced by wgrad_reduce_kernel).
-template <int STAGES>
 __global__ __launch_bounds__(576) void wgrad_rows_kernel(const uint16_t *__restrict__ dy,
                                                          const uint16_t *__restrict__ x,
                                                          float *__restrict__ part, void *__restrict__ dw,
                                                          const uint16_t *__restrict__ zero, RGeo g, int out_f32,
-                                                         int accumulate, int atomic_out, int stagger = 0) {
+                                                         int accumulate, int atomic_out, int stagger) {
+    constexpr int STAGES = 2;           // LDS ring depth (34 KB per stage)
     constexpr int ROW = 128;            // 64 channels
     constexpr int MAXP = 4;             // pieces per wave per K-step (9 * 4 >= 8 + 25)
     constexpr int STAGE = (8 + 25 + 1) * 1024;  // dy 8 KB | input image <= 25 KB | dummy 1 KB
@@ -342,9 +310,7 @@ __global__ __launch_bounds__(576) void wgrad_rows_kernel(const uint16_t *__restr
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // = tap
     const int kh = wave / 3, kw = wave - 3 * (wave / 3);
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    const int q8 = nwg >> 3, rr8 = nwg & 7, xcd = orig & 7;
-    const int wg = (xcd < rr8 ? xcd * (q8 + 1) : rr8 * (q8 + 1) + (xcd - rr8) * q8) + (orig >> 3);
+    const int wg = xcd_remap(blockIdx.x, gridDim.x);
     const int mn = g.mtiles * g.ntiles;
     const int split = wg / mn, ctile = wg - split * mn;
     const int mt = ctile / g.ntiles, nt = ctile - mt * g.ntiles;
@@ -554,7 +520,7 @@ __global__ __launch_bounds__(64 * NWV) void wgrad_rows_rect_kernel(const uint16_
                                                                    float *__restrict__ part, void *__restrict__ dw,
                                                                    const uint16_t *__restrict__ zero, RRGeo g,
                                                                    int out_f32, int accumulate, int atomic_out,
-                                                                   int stagger = 0) {
+                                                                   int stagger) {
     constexpr int ROW = 2 * CT;                    // staged bytes per pixel (CT channels)
     constexpr int TI = CT / 16;                    // 16-wide MFMA blocks per tile side
     constexpr int LPR = ROW / 16;                  // lanes (16 B each) per staged row
@@ -569,9 +535,7 @@ __global__ __launch_bounds__(64 * NWV) void wgrad_rows_rect_kernel(const uint16_
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    const int q8 = nwg >> 3, rr8 = nwg & 7, xcd = orig & 7;
-    const int wg = (xcd < rr8 ? xcd * (q8 + 1) : rr8 * (q8 + 1) + (xcd - rr8) * q8) + (orig >> 3);
+    const int wg = xcd_remap(blockIdx.x, gridDim.x);
     const int mn = g.mtiles * g.ntiles;
     const int per_split = mn * g.tgroups;
     const int split = wg / per_split, rem0 = wg - split * per_split;
@@ -1001,7 +965,7 @@ void launch_conv_wgrad(const uint16_t *dy, const uint16_t *x, void *dw, float *p
     case WgradKernel::Tiled: launch_tiled(dy, x, dw, part, plan, out_f32, accumulate, atomic_out, s); break;
     case WgradKernel::Rows3x3: {
         const RGeo &g = plan.rows;
-        wgrad_rows_kernel<2><<<g.mtiles * g.ntiles * g.splits, 576, 0, s>>>(
+        wgrad_rows_kernel<<<g.mtiles * g.ntiles * g.splits, 576, 0, s>>>(
             dy, x, part, dw, reinterpret_cast<const uint16_t *>(zero_page()), g, out_f32, accumulate, atomic_out, 1);
         if (g.splits > 1 && !atomic_out)
             reduce_tiles<1, 1>(part, dw, reduce_geo(g.C, g.K, g.mtiles, g.ntiles, 9, g.tiles, g.splits), out_f32, accumulate, s);

@@ -33,13 +33,11 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "mfma_util.hpp"
 
 namespace kfk {
 
 namespace {
-
-using bf16x8 = __attribute__((ext_vector_type(8))) short;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int kGM = 256;             // tile rows
 constexpr int kSlabK = 32;           // K per slab
@@ -48,15 +46,6 @@ constexpr int kRowB = kSlabK * 2;    // 64-byte slab rows
 constexpr int kABytes = kGM * kRowB; // 16 KB
 constexpr uint32_t kOOB = 0x80000000u;
 constexpr int kRsrcFlags = 0x00020000;
-
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-__device__ __forceinline__ __attribute__((address_space(3))) void *lds3(uint8_t *p) {
-    return (__attribute__((address_space(3))) void *)(p);
-}
 
 // byte offset of 16-byte chunk c (0..3) of slab row r.  ds_read_b128 serves a wave in four
 // lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31}, {32-35,44-47,52-59}, {36-43,48-51,60-63}
@@ -80,14 +69,14 @@ __device__ __forceinline__ void gemm_stage(uint8_t *lds, __amdgpu_buffer_rsrc_t 
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const uint32_t vo = a_off[i] == kOOB ? kOOB : a_off[i] + kb;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(ar, lds3(abase + (i * 8 + wave) * 1024), 16, vo, 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(ar, lds_ptr(abase + (i * 8 + wave) * 1024), 16, vo, 0, 0, 0);
     }
 #pragma unroll
     for (int i = 0; i < B_FULL; ++i)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(br, lds3(bbase + (i * 8 + wave) * 1024), 16, b_off[i] + kb, 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(br, lds_ptr(bbase + (i * 8 + wave) * 1024), 16, b_off[i] + kb, 0, 0, 0);
     if constexpr (B_REM != 0) {
         if (b_extra)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(br, lds3(bbase + (B_FULL * 8 + wave) * 1024), 16,
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(br, lds_ptr(bbase + (B_FULL * 8 + wave) * 1024), 16,
                                                      b_off[B_FULL] + kb, 0, 0, 0);
     }
 }
@@ -97,8 +86,8 @@ __device__ __forceinline__ void gemm_stage(uint8_t *lds, __amdgpu_buffer_rsrc_t 
 // outstanding LDS reads (lgkmcnt(0)) before every MFMA cluster of the two-set pipeline below,
 // including the next slab's reads issued just before -- so the kernel counts them itself
 // (gemm_wait_frags) and fences the MFMAs with sched_barrier (cdna_hip_programming.md §5.4 rule 18).
-__device__ __forceinline__ bf16x8 ds_read16(const uint8_t *p) {
-    bf16x8 v;
+__device__ __forceinline__ s16x8 ds_read16(const uint8_t *p) {
+    s16x8 v;
     const uint32_t a = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(p));
     asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(a) : "memory");
     return v;
@@ -106,7 +95,7 @@ __device__ __forceinline__ bf16x8 ds_read16(const uint8_t *p) {
 
 template <int TM, int TN>
 __device__ __forceinline__ void gemm_frags(const uint8_t *slot, int arow0, int bcol0, int frow, int fchk,
-                                           bf16x8 (&af)[TM], bf16x8 (&bf)[TN]) {
+                                           s16x8 (&af)[TM], s16x8 (&bf)[TN]) {
     const uint8_t *bbase = slot + kABytes;
 #pragma unroll
     for (int j = 0; j < TN; ++j) bf[j] = ds_read16(bbase + slab_off(bcol0 + j * 16 + frow, fchk));
@@ -124,7 +113,7 @@ __device__ __forceinline__ void gemm_wait_frags() {
 // transposed product (MFMA A operand = the B fragment): acc[i][j] holds C^T[n][m] of block (i, j),
 // lane -> m = lane & 15, n = (lane >> 4) * 4 + r
 template <int TM, int TN>
-__device__ __forceinline__ void gemm_mfma(f32x4 (&acc)[TM][TN], const bf16x8 (&af)[TM], const bf16x8 (&bf)[TN]) {
+__device__ __forceinline__ void gemm_mfma(f32x4 (&acc)[TM][TN], const s16x8 (&af)[TM], const s16x8 (&bf)[TN]) {
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -153,11 +142,11 @@ __device__ __forceinline__ void gemm_stage4(uint8_t *lds, __amdgpu_buffer_rsrc_t
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const uint32_t vo = (ghost || a_off[i] == kOOB) ? kOOB : a_off[i] + kb;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(ar, lds3(abase + (i * 4 + wave) * 1024), 16, vo, 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(ar, lds_ptr(abase + (i * 4 + wave) * 1024), 16, vo, 0, 0, 0);
     }
 #pragma unroll
     for (int i = 0; i < B_PER; ++i)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(br, lds3(bbase + (i * 4 + wave) * 1024), 16,
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(br, lds_ptr(bbase + (i * 4 + wave) * 1024), 16,
                                                  ghost ? kOOB : b_off[i] + kb, 0, 0, 0);
 }
 
@@ -165,7 +154,7 @@ __device__ __forceinline__ void gemm_stage4(uint8_t *lds, __amdgpu_buffer_rsrc_t
 // the A fragment may have just landed (a just-written operand before an MFMA, cdna_hip_programming.md
 // inline-asm item 2); the accumulate chains need no wait.
 template <int TN>
-__device__ __forceinline__ void mfma_row(f32x4 (&acc)[TN], const bf16x8 (&b)[TN], const bf16x8 &a) {
+__device__ __forceinline__ void mfma_row(f32x4 (&acc)[TN], const s16x8 (&b)[TN], const s16x8 &a) {
     static_assert(TN == 8 || TN == 4, "TN");
     if constexpr (TN == 8) {
         asm volatile(
@@ -220,11 +209,7 @@ __global__ __launch_bounds__(512) void gemm_nt_kernel(const uint16_t *__restrict
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 2, wn = wave & 3;
 
-    // bijective XCD remap: the blocks that share an XCD (orig % 8) get a contiguous run of tiles
-    const int nwg = mtiles * ntiles;
-    const int orig = blockIdx.x;
-    const int q = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
-    const int wgid = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (orig >> 3);
+    const int wgid = xcd_remap(blockIdx.x, mtiles * ntiles);
     const int mt = wgid / ntiles, nt = wgid - mt * ntiles;
     const int m0 = mt * kGM, n0 = nt * BN;
 
@@ -278,19 +263,19 @@ __global__ __launch_bounds__(512) void gemm_nt_kernel(const uint16_t *__restrict
     {
         const int later = slabs - 1 < 3 ? slabs - 1 : 3;
         if (full_b) {
-            if (later == 3) vm_wait<3 * (2 + BI)>();
-            else if (later == 2) vm_wait<2 * (2 + BI)>();
-            else if (later == 1) vm_wait<2 + BI>();
-            else vm_wait<0>();
+            if (later == 3) wait_vmcnt<3 * (2 + BI)>();
+            else if (later == 2) wait_vmcnt<2 * (2 + BI)>();
+            else if (later == 1) wait_vmcnt<2 + BI>();
+            else wait_vmcnt<0>();
         } else {
-            if (later == 3) vm_wait<3 * (2 + B_FULL)>();
-            else if (later == 2) vm_wait<2 * (2 + B_FULL)>();
-            else if (later == 1) vm_wait<2 + B_FULL>();
-            else vm_wait<0>();
+            if (later == 3) wait_vmcnt<3 * (2 + B_FULL)>();
+            else if (later == 2) wait_vmcnt<2 * (2 + B_FULL)>();
+            else if (later == 1) wait_vmcnt<2 + B_FULL>();
+            else wait_vmcnt<0>();
         }
     }
     __builtin_amdgcn_s_barrier();
-    bf16x8 a0[TM], b0[TN], a1[TM], b1[TN];
+    s16x8 a0[TM], b0[TN], a1[TM], b1[TN];
     gemm_frags<TM, TN>(lds, arow0, bcol0, frow, fchk, a0, b0);
 
     // step s: returns with the fragments of slab s+1 in (an, bn) (if it exists)
@@ -300,13 +285,13 @@ __global__ __launch_bounds__(512) void gemm_nt_kernel(const uint16_t *__restrict
         // wait for slab s+1: issued so far are slabs 0 .. min(s + 3, slabs - 1)
         const int later = (slabs - 1 < s + 3 ? slabs - 1 : s + 3) - (s + 1);
         if (full_b) {
-            if (later >= 2) vm_wait<2 * (2 + BI)>();
-            else if (later == 1) vm_wait<2 + BI>();
-            else vm_wait<0>();
+            if (later >= 2) wait_vmcnt<2 * (2 + BI)>();
+            else if (later == 1) wait_vmcnt<2 + BI>();
+            else wait_vmcnt<0>();
         } else {
-            if (later >= 2) vm_wait<2 * (2 + B_FULL)>();
-            else if (later == 1) vm_wait<2 + B_FULL>();
-            else vm_wait<0>();
+            if (later >= 2) wait_vmcnt<2 * (2 + B_FULL)>();
+            else if (later == 1) wait_vmcnt<2 + B_FULL>();
+            else wait_vmcnt<0>();
         }
         __builtin_amdgcn_s_barrier();  // raw barrier: the later slabs' LDS-DMA stays in flight
         __builtin_amdgcn_sched_barrier(0);
@@ -478,10 +463,7 @@ __global__ __launch_bounds__(256) void gemm_nt4_kernel(const uint16_t *__restric
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    const int nwg = mtiles * ntiles;
-    const int orig = blockIdx.x;
-    const int q = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
-    const int wgid = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (orig >> 3);
+    const int wgid = xcd_remap(blockIdx.x, mtiles * ntiles);
     const int mt = wgid / ntiles, nt = wgid - mt * ntiles;
     const int m0 = mt * kGM, n0 = nt * BN;
 
@@ -516,14 +498,14 @@ __global__ __launch_bounds__(256) void gemm_nt4_kernel(const uint16_t *__restric
     // slabs is even (K % 64 == 0, launch_gemm_nt): every step below runs both halves, no branch
 #pragma unroll
     for (int p = 0; p < kSlots - 1; ++p) gemm_stage4<BN>(lds, ar, br, a_off, b_off, wave, p, p, p >= slabs);
-    vm_wait<3 * PER>();
+    wait_vmcnt<3 * PER>();
     __builtin_amdgcn_s_barrier();
-    bf16x8 af[TM], b0[TN], b1[TN];
+    s16x8 af[TM], b0[TN], b1[TN];
     gemm_frags<TM, TN>(lds, arow0, bcol0, frow, fchk, af, b0);
 
     int slot_next = 1, slot_stage = 4;
     auto pre = [&](int s) {
-        vm_wait<2 * PER>();  // slab s + 1 landed (ghost slabs keep the count uniform at the tail)
+        wait_vmcnt<2 * PER>();  // slab s + 1 landed (ghost slabs keep the count uniform at the tail)
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         gemm_stage4<BN>(lds, ar, br, a_off, b_off, wave, s + 4, slot_stage, s + 4 >= slabs);
@@ -532,7 +514,7 @@ __global__ __launch_bounds__(256) void gemm_nt4_kernel(const uint16_t *__restric
     // per slab: the next slab's B fragments into the other B set, then row block i's MFMAs and the
     // next slab's A fragment i read in place behind them; before row block i the reads newer than
     // this slab's A fragment i are its 7 - i successors, the TN next-B reads and i next-A reads
-    auto half = [&](bf16x8 (&bc)[TN], bf16x8 (&bn)[TN]) {
+    auto half = [&](s16x8 (&bc)[TN], s16x8 (&bn)[TN]) {
         const uint8_t *nslot = lds + slot_next * SLOT;
 #pragma unroll
         for (int j = 0; j < TN; ++j) bn[j] = ds_read16(nslot + kABytes + slab_off(bcol0 + j * 16 + frow, fchk));
@@ -554,7 +536,7 @@ __global__ __launch_bounds__(256) void gemm_nt4_kernel(const uint16_t *__restric
         slot_next = slot_next == kSlots - 1 ? 0 : slot_next + 1;
         slot_stage = slot_stage == kSlots - 1 ? 0 : slot_stage + 1;
     }
-    vm_wait<0>();  // the ghost slabs' loads
+    wait_vmcnt<0>();  // the ghost slabs' loads
     // the last (unused) prefetch reads, and 16 wait states before the accumulators are read (an
     // MFMA's result -> a non-MFMA reader: 12 states for the 8-pass XDL ops)
     asm volatile("s_waitcnt lgkmcnt(0)\n s_nop 7\n s_nop 7" ::: "memory");

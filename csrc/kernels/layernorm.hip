@@ -32,18 +32,6 @@ namespace {
 
 constexpr int kLnWaves = 4;  // waves (rows in flight) per block
 
-__device__ __forceinline__ void unpack4(const uint2 &v, float (&f)[4]) {
-    f[0] = __uint_as_float(v.x << 16);
-    f[1] = __uint_as_float(v.x & 0xffff0000u);
-    f[2] = __uint_as_float(v.y << 16);
-    f[3] = __uint_as_float(v.y & 0xffff0000u);
-}
-
-__device__ __forceinline__ uint2 pack4(const float (&f)[4]) {
-    return make_uint2(pack_bf16x2(f[0], f[1]),
-                      pack_bf16x2(f[2], f[3]));
-}
-
 struct LnDrop {
     uint32_t seed = 0, thresh = 0;  // keep(e) <=> hash(seed, e) >= thresh (thresh = p * 2^32)
     float inv_keep = 1.f;
@@ -92,10 +80,10 @@ __global__ __launch_bounds__(64 * kLnWaves) void ln_fwd_kernel(const uint2 *__re
         float sum = 0.f;
 #pragma unroll
         for (int j = 0; j < G; ++j) {
-            unpack4(x[base + j * 64 + lane], v[j]);
+            unpack_bf16x4(x[base + j * 64 + lane], v[j]);
             if (r) {
                 float t[4];
-                unpack4(r[base + j * 64 + lane], t);
+                unpack_bf16x4(r[base + j * 64 + lane], t);
                 if (drop.on) {
                     const int64_t e0 = (base + j * 64 + lane) * 4;
 #pragma unroll
@@ -105,9 +93,9 @@ __global__ __launch_bounds__(64 * kLnWaves) void ln_fwd_kernel(const uint2 *__re
                 for (int k = 0; k < 4; ++k) v[j][k] += t[k];
             }
             // the residual stream is bf16: normalise exactly the values that are stored
-            uint2 sv = pack4(v[j]);
+            uint2 sv = pack_bf16x4(v[j]);
             if (s_out) s_out[base + j * 64 + lane] = sv;
-            unpack4(sv, v[j]);
+            unpack_bf16x4(sv, v[j]);
 #pragma unroll
             for (int k = 0; k < 4; ++k) sum += v[j][k];
         }
@@ -126,7 +114,7 @@ __global__ __launch_bounds__(64 * kLnWaves) void ln_fwd_kernel(const uint2 *__re
             float o[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) o[k] = (v[j][k] - mu) * rs * gm[j][k] + bt[j][k];
-            y[base + j * 64 + lane] = pack4(o);
+            y[base + j * 64 + lane] = pack_bf16x4(o);
         }
         if (lane == 0) {
             mean[row] = mu;
@@ -167,8 +155,8 @@ __global__ __launch_bounds__(64 * kLnWaves) void ln_bwd_kernel(const uint2 *__re
 #pragma unroll
         for (int j = 0; j < G; ++j) {
             float d[4], xv[4];
-            unpack4(dy[base + j * 64 + lane], d);
-            unpack4(s[base + j * 64 + lane], xv);
+            unpack_bf16x4(dy[base + j * 64 + lane], d);
+            unpack_bf16x4(s[base + j * 64 + lane], xv);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 xh[j][k] = (xv[k] - mu) * rs;
@@ -185,18 +173,18 @@ __global__ __launch_bounds__(64 * kLnWaves) void ln_bwd_kernel(const uint2 *__re
             float o[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) o[k] = rs * (g[j][k] - m1 - xh[j][k] * m2);
-            uint2 pk = pack4(o);
+            uint2 pk = pack_bf16x4(o);
             ds[base + j * 64 + lane] = pk;
             if (dr) {  // gradient of the dropped residual input
                 const int64_t e0 = (base + j * 64 + lane) * 4;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) o[k] = ln_keep(drop, e0 + k) ? o[k] * drop.inv_keep : 0.f;
-                pk = pack4(o);
+                pk = pack_bf16x4(o);
                 dr[base + j * 64 + lane] = pk;
             }
             if constexpr (RB) {
                 float w[4];
-                unpack4(pk, w);  // the bf16 values the producing linear's backward consumes
+                unpack_bf16x4(pk, w);  // the bf16 values the producing linear's backward consumes
 #pragma unroll
                 for (int k = 0; k < 4; ++k) rb[j][k] += w[k];
             }

@@ -273,15 +273,6 @@ void launch_gns_update(const float *sumsq_small, const float *sumsq_big, float b
 namespace {
 constexpr int kColVec = 64;  // 8-column vectors per block (512 columns)
 
-__device__ __forceinline__ void add8(const uint4 &q, float (&acc)[8]) {
-    const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        acc[2 * k] += __uint_as_float(w[k] << 16);
-        acc[2 * k + 1] += __uint_as_float(w[k] & 0xffff0000u);
-    }
-}
-
 __global__ __launch_bounds__(256) void colsum_stage1(const uint4 *__restrict__ x, int64_t T, int OV, int rows_per,
                                                      float *__restrict__ part) {
     const int v = blockIdx.y * kColVec + (threadIdx.x % kColVec);
@@ -299,10 +290,10 @@ __global__ __launch_bounds__(256) void colsum_stage1(const uint4 *__restrict__ x
 #pragma unroll
             for (int u = 0; u < 4; ++u) q[u] = x[(r + 4 * u) * OV + v];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) add8(q[u], acc);
+            for (int u = 0; u < 4; ++u) add_bf16x8(q[u], acc);
         }
         for (; r < r1; r += 4) {
-            add8(x[r * OV + v], acc);
+            add_bf16x8(x[r * OV + v], acc);
         }
     }
     __shared__ float red[4][kColVec * 8];

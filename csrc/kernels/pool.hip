@@ -20,9 +20,6 @@ namespace kfk {
 
 namespace {
 
-__device__ __forceinline__ float lo16(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float hi16(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-
 struct PoolGeo {
     int H, W, OH, OW, CV;
     int64_t nout;  // N * OH * OW * CV
@@ -54,14 +51,14 @@ __global__ __launch_bounds__(kBlock) void maxpool2_fwd_kernel(const uint4 *__res
         uint32_t out[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            float ml = lo16(bits_of(v[0], k)), mh = hi16(bits_of(v[0], k));
+            float ml = bf16_lo(bits_of(v[0], k)), mh = bf16_hi(bits_of(v[0], k));
             uint32_t bl = bits_of(v[0], k) & 0xffffu, bh = bits_of(v[0], k) >> 16;
 #pragma unroll
             for (int p = 1; p < 4; ++p) {
                 const uint32_t w = bits_of(v[p], k);
                 // NaN propagates like torch's max-pool: a NaN always takes the window
-                if (lo16(w) > ml || isnan(lo16(w))) ml = lo16(w), bl = w & 0xffffu;
-                if (hi16(w) > mh || isnan(hi16(w))) mh = hi16(w), bh = w >> 16;
+                if (bf16_lo(w) > ml || isnan(bf16_lo(w))) ml = bf16_lo(w), bl = w & 0xffffu;
+                if (bf16_hi(w) > mh || isnan(bf16_hi(w))) mh = bf16_hi(w), bh = w >> 16;
             }
             out[k] = bl | (bh << 16);
         }
@@ -90,20 +87,20 @@ __global__ __launch_bounds__(kBlock) void maxpool2_bwd_kernel(const uint4 *__res
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             // first maximum per half-word, as the forward chose it
-            float ml = lo16(bits_of(v[0], k)), mh = hi16(bits_of(v[0], k));
+            float ml = bf16_lo(bits_of(v[0], k)), mh = bf16_hi(bits_of(v[0], k));
             int pl = 0, ph = 0;
 #pragma unroll
             for (int p = 1; p < 4; ++p) {
                 const uint32_t w = bits_of(v[p], k);
-                if (lo16(w) > ml || isnan(lo16(w))) ml = lo16(w), pl = p;
-                if (hi16(w) > mh || isnan(hi16(w))) mh = hi16(w), ph = p;
+                if (bf16_lo(w) > ml || isnan(bf16_lo(w))) ml = bf16_lo(w), pl = p;
+                if (bf16_hi(w) > mh || isnan(bf16_hi(w))) mh = bf16_hi(w), ph = p;
             }
             uint32_t gw = bits_of(gv, k);
             if constexpr (GATE) {
                 if (ml <= 0.f) gw &= 0xffff0000u;
                 if (mh <= 0.f) gw &= 0xffffu;
-                csum[2 * k] += lo16(gw);
-                csum[2 * k + 1] += hi16(gw);
+                csum[2 * k] += bf16_lo(gw);
+                csum[2 * k + 1] += bf16_hi(gw);
             }
 #pragma unroll
             for (int p = 0; p < 4; ++p)
@@ -171,7 +168,7 @@ __global__ __launch_bounds__(kBlock) void maxpool3s2_fwd_kernel(const uint4 *__r
                 const uint4 v = x[((n * g.H + h) * g.W + w) * g.CV + cv];
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
-                    const float f = (k & 1) ? hi16(bits_of(v, k >> 1)) : lo16(bits_of(v, k >> 1));
+                    const float f = (k & 1) ? bf16_hi(bits_of(v, k >> 1)) : bf16_lo(bits_of(v, k >> 1));
                     if (f > best[k] || isnan(f)) {  // torch: a later NaN takes over
                         best[k] = f;
                         a[k] = kh * 3 + kw;
@@ -221,7 +218,7 @@ __global__ __launch_bounds__(kBlock) void maxpool3s2_bwd_kernel(const uint4 *__r
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
                     const uint32_t ak = ((k < 4 ? am.x : am.y) >> (8 * (k & 3))) & 0xffu;
-                    const float f = (k & 1) ? hi16(bits_of(d, k >> 1)) : lo16(bits_of(d, k >> 1));
+                    const float f = (k & 1) ? bf16_hi(bits_of(d, k >> 1)) : bf16_lo(bits_of(d, k >> 1));
                     acc[k] += ak == me ? f : 0.f;
                 }
             }
@@ -258,7 +255,7 @@ __global__ __launch_bounds__(kBlock) void avgpool3s1_kernel(const uint4 *__restr
                 const uint4 v = x[((nn * H + hh) * W + ww) * CV + cv];
 #pragma unroll
                 for (int k = 0; k < 8; ++k)
-                    acc[k] += (k & 1) ? hi16(bits_of(v, k >> 1)) : lo16(bits_of(v, k >> 1));
+                    acc[k] += (k & 1) ? bf16_hi(bits_of(v, k >> 1)) : bf16_lo(bits_of(v, k >> 1));
             }
         }
         constexpr float inv9 = 1.f / 9.f;
@@ -291,12 +288,12 @@ __global__ __launch_bounds__(kBlock) void gap_fwd_kernel(const uint4 *__restrict
 #pragma unroll
             for (int u = 0; u < 4; ++u)
 #pragma unroll
-                for (int k = 0; k < 8; ++k) acc[k] += (k & 1) ? hi16(bits_of(v[u], k >> 1)) : lo16(bits_of(v[u], k >> 1));
+                for (int k = 0; k < 8; ++k) acc[k] += (k & 1) ? bf16_hi(bits_of(v[u], k >> 1)) : bf16_lo(bits_of(v[u], k >> 1));
         }
         for (; q < HW; ++q) {
             const uint4 v = p[static_cast<int64_t>(q) * CV];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) acc[k] += (k & 1) ? hi16(bits_of(v, k >> 1)) : lo16(bits_of(v, k >> 1));
+            for (int k = 0; k < 8; ++k) acc[k] += (k & 1) ? bf16_hi(bits_of(v, k >> 1)) : bf16_lo(bits_of(v, k >> 1));
         }
         uint32_t o[4];
 #pragma unroll
@@ -317,8 +314,8 @@ __global__ __launch_bounds__(kBlock) void gap_bwd_kernel(const uint4 *__restrict
         uint32_t o[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k)
-            o[k] = static_cast<uint32_t>(f32_to_bf16(lo16(bits_of(d, k)) * inv)) |
-                   (static_cast<uint32_t>(f32_to_bf16(hi16(bits_of(d, k)) * inv)) << 16);
+            o[k] = static_cast<uint32_t>(f32_to_bf16(bf16_lo(bits_of(d, k)) * inv)) |
+                   (static_cast<uint32_t>(f32_to_bf16(bf16_hi(bits_of(d, k)) * inv)) << 16);
         dx[i] = make_uint4(o[0], o[1], o[2], o[3]);
     }
 }

@@ -26,18 +26,13 @@
 // benchmarks/system/benchmark_kungfu.py:96).
 #include "common.hpp"
 #include "kernels.hpp"
+#include "mfma_util.hpp"
 
 #include <stdexcept>
 
 namespace kfk {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 constexpr int kKH = 7;           // window rows (one K-step each)
 constexpr int kKPad = 224;       // K = 7 kh x 8 kw x 4 c
@@ -46,35 +41,8 @@ constexpr int kCout = 64;
 
 struct StemGeo {
     int N, H, W, OH, OW, M;
-    uint64_t m_hw, m_ow;  // floor division magics (see conv_wgrad.hip)
+    uint64_t m_hw, m_ow;  // floor division magics (fdiv)
 };
-
-__device__ __forceinline__ int fdiv(int p, uint64_t m) {
-    return static_cast<int>((static_cast<uint64_t>(static_cast<uint32_t>(p)) * m) >> 40);
-}
-
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-
-// two f32 -> packed bf16 pair (round to nearest even): one v_cvt_pk_bf16_f32 on gfx950.  Shadows
-// common.hpp's integer-rounding pack_bf16x2 inside this file: here (stem forward epilogue, the BNP dx)
-// the instruction measured faster (r6t15: ResNet-50 20.24-20.27 vs 20.35-20.42 ms/step with attention /
-// stem / stem3 on it), while in gemm.hip's epilogues it measured 6.5x slower (r6t14)
-__device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {
-    const bf16x2 v = __builtin_convertvector(f32x2{a, b}, bf16x2);
-    return __builtin_bit_cast(uint32_t, v);
-}
-
-__device__ __forceinline__ void unpack8(const uint4 &v, float (&f)[8]) {
-    const uint32_t *u = reinterpret_cast<const uint32_t *>(&v);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        f[2 * k] = __uint_as_float(u[k] << 16);
-        f[2 * k + 1] = __uint_as_float(u[k] & 0xffff0000u);
-    }
-}
 
 // x [P, 3] -> x4 [P, 4] (4th channel 0); two pixels per thread (12-byte aligned reads).
 __global__ void stem_pad4_kernel(const uint32_t *__restrict__ x, uint4 *__restrict__ x4, int64_t npairs,
@@ -130,9 +98,7 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(const uint16_t *__restric
     __shared__ __attribute__((aligned(16))) uint8_t lds[2 * kAStage + kCout * kBRow];
     uint8_t *bimg = lds + 2 * kAStage;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    const int q8 = nwg >> 3, rr = nwg & 7, xcd = orig & 7;
-    const int mt = (xcd < rr ? xcd * (q8 + 1) : rr * (q8 + 1) + (xcd - rr) * q8) + (orig >> 3);
+    const int mt = xcd_remap(blockIdx.x, gridDim.x);
     const int m0 = mt * BM;
 
     // packed weights -> LDS (once)
@@ -403,8 +369,8 @@ __global__ __launch_bounds__(512) void stem_fwd_rows_kernel(const uint16_t *__re
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     // v_cvt_pk_bf16_f32 (RNE, two values per instruction); statistics of the stored values
-                    const uint32_t lo = pack_bf16x2(acc[i][0], acc[i][1]);
-                    const uint32_t hi = pack_bf16x2(acc[i][2], acc[i][3]);
+                    const uint32_t lo = pack_bf16x2_hw(acc[i][0], acc[i][1]);
+                    const uint32_t hi = pack_bf16x2_hw(acc[i][2], acc[i][3]);
                     const float f0 = __uint_as_float(lo << 16), f1 = __uint_as_float(lo & 0xffff0000u);
                     const float f2 = __uint_as_float(hi << 16), f3 = __uint_as_float(hi & 0xffff0000u);
                     s1[i][0] += f0;
@@ -484,19 +450,6 @@ constexpr int kBK = 64;               // pixels per K-step
 constexpr int kARow = 128;            // dy image: 64 channels
 constexpr int kIRow = 512;            // im2col image: 256 k (224 used)
 constexpr int kWStage = kBK * (kARow + kIRow);  // 40 KB
-
-template <int ROW>
-__device__ __forceinline__ int hswz(int row) {
-    if constexpr (ROW == 128) return ((row >> 1) & 1) | (((row >> 3) & 1) << 1);
-    else return (row & 3) | (((row >> 3) & 1) << 2);  // 256- and 512-byte rows: 8 groups per bank row
-}
-
-__device__ __forceinline__ bf16x8 tr_frag(const uint8_t *p0, const uint8_t *p1) {
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(p0));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(p1));
-    const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8, v);
-}
 
 // grid = splits; tile = 64 co x 256 k (wave w: k in [64w, 64w + 64); wave 3 uses k < 224 only)
 __global__ __launch_bounds__(256) void stem_wgrad_kernel(const uint16_t *__restrict__ dy,
@@ -675,15 +628,6 @@ struct StemBnp {
 constexpr int kPoolD = 64 * 128;               // slot: dyp row [PW <= 64][64] bf16 ...
 constexpr int kPoolSlot = kPoolD + 64 * 64;    // ... + argmax row [PW][64] bytes
 
-__device__ __forceinline__ void unpack8f(const uint4 &v, float (&f)[8]) {
-    const uint32_t u[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = __uint_as_float(u[i] << 16);
-        f[2 * i + 1] = __uint_as_float(u[i] & 0xffff0000u);
-    }
-}
-
 // 16-bit lane masks of the argmax bytes equal to kk: for the 4 bytes of a (channels 4 q .. 4 q + 3),
 // lo = [ch 0 | ch 1] and hi = [ch 2 | ch 3] as 0xffff / 0 halves (SWAR zero-byte test of a ^ kk, then
 // v_perm_b32's sign-replicating selectors 8..11 spread each byte's flag; ~8 ops for 4 channels against
@@ -732,7 +676,7 @@ __device__ __forceinline__ void pool_grad8(const uint8_t *pool, int PH, int PW, 
             argmax_masks(am.x, kk, m0, m1);
             argmax_masks(am.y, kk, m2, m3);
             float d[8];
-            unpack8f(make_uint4(dv.x & m0, dv.y & m1, dv.z & m2, dv.w & m3), d);
+            unpack_bf16x8(make_uint4(dv.x & m0, dv.y & m1, dv.z & m2, dv.w & m3), d);
 #pragma unroll
             for (int k = 0; k < 8; ++k) g[k] += d[k];
         }
@@ -747,7 +691,7 @@ constexpr int kBnpCoef = 5 * kCout;
 // kc = the LDS coefficient table
 __device__ __forceinline__ uint4 bnp_dx(const float *kc, int cv, const uint4 &yv, float (&g)[8]) {
     float xv[8];
-    unpack8f(yv, xv);
+    unpack_bf16x8(yv, xv);
     float o[8];
     // (scalar reads of the table, not a [5][8] array: the array was promoted to LDS)
 #pragma unroll
@@ -756,8 +700,8 @@ __device__ __forceinline__ uint4 bnp_dx(const float *kc, int cv, const uint4 &yv
         g[k] = (xv[k] * t[0] + t[kCout]) > 0.f ? g[k] : 0.f;
         o[k] = t[2 * kCout] * g[k] + t[3 * kCout] * xv[k] + t[4 * kCout];
     }
-    return make_uint4(pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]), pack_bf16x2(o[4], o[5]),
-                      pack_bf16x2(o[6], o[7]));
+    return make_uint4(pack_bf16x2_hw(o[0], o[1]), pack_bf16x2_hw(o[2], o[3]), pack_bf16x2_hw(o[4], o[5]),
+                      pack_bf16x2_hw(o[6], o[7]));
 }
 
 template <bool BNP>

@@ -34,6 +34,7 @@
 // Cout-32 kernel as it was.
 #include "common.hpp"
 #include "kernels.hpp"
+#include "mfma_util.hpp"
 
 #include <stdexcept>
 
@@ -41,24 +42,12 @@ namespace kfk {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
 constexpr int kKp = 64;       // padded K: 4 kh x 4 kw x 4 c
 constexpr int kRowS = 144;    // LDS bytes per transposed row (64 pixels x 2 B + 16 pad)
 
 struct S3Geo {
     int N, H, W, OH, OW, M, KH, KW, stride, ph, pw;
 };
-
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-
-// two f32 -> packed bf16 pair (round to nearest even: v_cvt_pk_bf16_f32), schedulable like any other op
-__device__ __forceinline__ uint32_t pk2(float a, float b) {
-    const bf16x2 v = __builtin_convertvector(f32x2{a, b}, bf16x2);
-    return __builtin_bit_cast(uint32_t, v);
-}
 
 __device__ __forceinline__ float ldf(const float *p) { return *p; }
 __device__ __forceinline__ float ldf(const uint16_t *p) { return __uint_as_float(static_cast<uint32_t>(*p) << 16); }
@@ -85,7 +74,8 @@ __device__ __forceinline__ void im2col_raw(const T *__restrict__ x, const S3Geo 
 
 // the 8 bf16 of a chunk (a zero 4th channel per pixel)
 __device__ __forceinline__ uint4 pack_chunk(const float (&v)[6]) {
-    return make_uint4(pk2(v[0], v[1]), pk2(v[2], 0.f), pk2(v[3], v[4]), pk2(v[5], 0.f));
+    return make_uint4(pack_bf16x2_hw(v[0], v[1]), pack_bf16x2_hw(v[2], 0.f), pack_bf16x2_hw(v[3], v[4]),
+                      pack_bf16x2_hw(v[5], 0.f));
 }
 
 template <class T>
@@ -187,8 +177,8 @@ __global__ __launch_bounds__(256) void stem3_fwd_kernel(const T *__restrict__ x,
                         if (relu && v[t] <= 0.f) v[t] = 0.f;  // keeps NaN, as torch.relu
                     }
                 }
-                w[2 * j] = pk2(v[0], v[1]);
-                w[2 * j + 1] = pk2(v[2], v[3]);
+                w[2 * j] = pack_bf16x2_hw(v[0], v[1]);
+                w[2 * j + 1] = pack_bf16x2_hw(v[2], v[3]);
             }
 #pragma unroll
             for (int u = 0; u < JB / 2; ++u)

@@ -96,15 +96,6 @@ __global__ __launch_bounds__(kXBlock) void xent_bwd_kernel(const uint32_t *__res
 
 // Rows padded to a multiple of 8 classes (ld % 8 == 0: the vocabulary-projection GEMM's padded
 // logits, gemm_nt_ld): 16-byte loads, four in flight per lane; classes >= V of the last chunk masked.
-__device__ __forceinline__ void bf8_unpack(const uint4 v, float (&f)[8]) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        f[2 * k] = __uint_as_float(w[k] << 16);
-        f[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
-    }
-}
-
 __global__ __launch_bounds__(kXBlock) void xent_fwd_vec_kernel(const uint16_t *__restrict__ x,
                                                               const int64_t *__restrict__ labels, int V, int64_t ld,
                                                               float *__restrict__ lse, float *__restrict__ loss) {
@@ -115,7 +106,7 @@ __global__ __launch_bounds__(kXBlock) void xent_fwd_vec_kernel(const uint16_t *_
     float m = -INFINITY, s = 0.f;
     auto fold = [&](const uint4 v, int c) {
         float f[8];
-        bf8_unpack(v, f);
+        unpack_bf16x8(v, f);
         float mx = -INFINITY;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
@@ -175,7 +166,7 @@ __global__ __launch_bounds__(kXBlock) void xent_bwd_vec_kernel(const uint16_t *_
     const int nch = (V + 7) / 8;
     auto grad = [&](const uint4 v, int c) {
         float f[8];
-        bf8_unpack(v, f);
+        unpack_bf16x8(v, f);
         uint32_t w[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
