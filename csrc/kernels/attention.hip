@@ -1,6 +1,7 @@
 // Fused multi-head self-attention (forward + backward) for BERT-sized sequences on gfx950:
 // S = 64 or 128 tokens, head dim 64, bf16, dropout on the attention probabilities, no mask.
-// (Longer sequences, up to 512: the streaming kernels of attention_long.hip, dispatched below.)
+// (Longer sequences, up to 512: the streaming kernels of attention_long.hip, dispatched below; padded
+// batches with per-sequence lengths, S >= 128: their length-aware twins in attention_lengths.hip.)
 //
 // Why: at S = 128 the whole per-(sequence, head) problem is 16 KB per operand, yet torch's
 // flash-attention backward on ROCm took 248 us per layer for BERT-base at batch 128 (12.5 % of
@@ -331,8 +332,9 @@ bool attention_supported(int S, int head_dim) {
 }
 
 void launch_attention_forward(const uint16_t *qkv, uint16_t *out, float *lse, int B, int S, int H, float scale,
-                              uint32_t seed, float p_drop, hipStream_t s, bool stream_kernel) {
+                              uint32_t seed, float p_drop, hipStream_t s, bool stream_kernel, const int *lengths) {
     check_length(S, stream_kernel);
+    if (lengths) return launch_attention_lengths_forward(qkv, out, lse, lengths, B, S, H, scale, seed, p_drop, s);
     if (!whole_sequence(S) || stream_kernel)
         return launch_attention_long_forward(qkv, out, lse, B, S, H, scale, seed, p_drop, s);
     const AttnArgs a = make_args(qkv, out, lse, nullptr, nullptr, H, scale, seed, p_drop);
@@ -342,8 +344,10 @@ void launch_attention_forward(const uint16_t *qkv, uint16_t *out, float *lse, in
 
 void launch_attention_backward(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *dout,
                                uint16_t *dqkv, int B, int S, int H, float scale, uint32_t seed, float p_drop,
-                               hipStream_t s, float *dsum, bool stream_kernel) {
+                               hipStream_t s, float *dsum, bool stream_kernel, const int *lengths) {
     check_length(S, stream_kernel);
+    if (lengths)
+        return launch_attention_lengths_backward(qkv, out, lse, dout, dqkv, dsum, lengths, B, S, H, scale, seed, p_drop, s);
     if (!whole_sequence(S) || stream_kernel)
         return launch_attention_long_backward(qkv, out, lse, dout, dqkv, dsum, B, S, H, scale, seed, p_drop, s);
     AttnArgs a = make_args(qkv, const_cast<uint16_t *>(out), const_cast<float *>(lse), dout, dqkv, H, scale, seed,

@@ -1,7 +1,7 @@
 // Device helpers shared by the fused attention kernels (attention.hip: whole sequence in LDS,
-// attention_long.hip: streamed blocks): the swizzled LDS image addressing, the MFMA operand
+// attention_long.hip and attention_lengths.hip: streamed blocks): the swizzled LDS image addressing, the MFMA operand
 // fragments, the dropout hash, the LDS-DMA staging and the kernel argument block.  Private to
-// those two files: everything sits in an unnamed namespace.
+// those files: everything sits in an unnamed namespace.
 #pragma once
 #include "common.hpp"
 #include "kernels.hpp"
@@ -116,5 +116,11 @@ void launch_attention_long_forward(const uint16_t *qkv, uint16_t *out, float *ls
 void launch_attention_long_backward(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *dout,
                                     uint16_t *dqkv, float *dsum, int B, int S, int H, float scale, uint32_t seed,
                                     float p_drop, hipStream_t s);
+// attention_lengths.hip: the same family with per-sequence lengths (int32 [B] on the device, clamped to [0, S])
+void launch_attention_lengths_forward(const uint16_t *qkv, uint16_t *out, float *lse, const int *lengths, int B, int S,
+                                      int H, float scale, uint32_t seed, float p_drop, hipStream_t s);
+void launch_attention_lengths_backward(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *dout,
+                                       uint16_t *dqkv, float *dsum, const int *lengths, int B, int S, int H,
+                                       float scale, uint32_t seed, float p_drop, hipStream_t s);
 
 }  // namespace kfk

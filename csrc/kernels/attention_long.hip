@@ -30,24 +30,17 @@
 // Between writing and reading the P / dS images the dK/dV kernel needs a second barrier (one that
 // leaves the DMA in flight); in the forward and the dQ kernel those rows never leave their wave.
 // Trip counts depend on S only.  All lengths are multiples of the block sizes, so no row index leaves [0, S).
-#include "attention_common.hpp"
+//
+// Padded batches (a per-sequence length below S) run the length-aware twins of these three kernels in
+// attention_lengths.hip; the block constants and the backward's per-block helpers both files use are
+// in attention_stream.hpp.  The kernels here are what a call without lengths runs, unchanged.
+#include "attention_stream.hpp"
 
 #include <stdexcept>
 
 namespace kfk {
 
 namespace {
-
-constexpr int BK = 64;          // rows of a streamed block (and of every resident backward block)
-constexpr int BLK = BK * 128;   // bytes of one 64-row image
-constexpr int TK = BK / 16;
-
-// Orders a wave's own LDS writes before its own later reads of them (the forward's P rows and the dQ
-// kernel's dS rows never leave their wave): no workgroup barrier, and no drain of the DMA in flight.
-__device__ __forceinline__ void lds_wave_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-// Workgroup barrier that publishes LDS writes only: unlike __syncthreads it leaves the LDS-DMA of the
-// next block in flight (that one is waited for, counted, at the top of the next step).
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 template <int BQ>
 __global__ __launch_bounds__(256) void attn_long_fwd_kernel(AttnArgs a, int S) {
@@ -166,78 +159,6 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(AttnArgs a, int S) {
                 make_uint2(pack_bf16x2_hw(o[c][i][0] * inv, o[c][i][1] * inv),
                            pack_bf16x2_hw(o[c][i][2] * inv, o[c][i][3] * inv));
         }
-    }
-}
-
-// S^T and dP^T of 16 queries (rows qw0.. of Qi / Oi) against the 64 keys of a block, as attention.hip's
-// backward phase 1: sc / dp[j] hold keys 16 j + 4 lg + r of query qw0 + lc.
-__device__ __forceinline__ void bwd_block_products(const uint8_t *Qi, const uint8_t *Oi, const uint8_t *Ki,
-                                                   const uint8_t *Vi, int qw0, int lane, f32x4 (&sc)[TK],
-                                                   f32x4 (&dp)[TK]) {
-#pragma unroll
-    for (int j = 0; j < TK; ++j) sc[j] = dp[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < DH / 32; ++s) {
-        const bf16x8 qa = row_frag<128>(Qi, qw0, 32 * s, lane);
-        const bf16x8 ga = row_frag<128>(Oi, qw0, 32 * s, lane);
-        bf16x8 kf[TK], vf[TK];
-#pragma unroll
-        for (int j = 0; j < TK; ++j) {
-            kf[j] = row_frag<128>(Ki, 16 * j, 32 * s, lane);
-            vf[j] = row_frag<128>(Vi, 16 * j, 32 * s, lane);
-        }
-#pragma unroll
-        for (int j = 0; j < TK; ++j) {
-            sc[j] = mfma(kf[j], qa, sc[j]);
-            dp[j] = mfma(vf[j], ga, dp[j]);
-        }
-    }
-}
-
-// This lane's share of D[q] = sum_key P_drop[q][key] dP[q][key] over the block (= rowsum(dO o O) with
-// the f32 O; the saved bf16 O would put its rounding into dS = P o (dP - D), which cancels where the
-// softmax is nearly one-hot).
-__device__ __forceinline__ float bwd_block_dsum(const AttnArgs &a, uint32_t seed, int bh, const uint8_t *Qi,
-                                                const uint8_t *Oi, const uint8_t *Ki, const uint8_t *Vi, int qw0,
-                                                int row, int key0, float l, int lane) {
-    const int lg = lane >> 4;
-    f32x4 sc[TK], dp[TK];
-    bwd_block_products(Qi, Oi, Ki, Vi, qw0, lane, sc, dp);
-    float t = 0.f;
-#pragma unroll
-    for (int j = 0; j < TK; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float p = __expf(sc[j][r] * a.scale - l);
-            if (keep_elem(seed, bh, row, key0 + 16 * j + 4 * lg + r, a.thresh)) t += p * dp[j][r];
-        }
-    return t * a.inv_keep;
-}
-
-// P and dS^T of the same 16 x 64 tile.  Writes dS (and P_drop when Pi) rows qw0 + lc of the images.
-__device__ __forceinline__ void bwd_block_scores(const AttnArgs &a, uint32_t seed, int bh, const uint8_t *Qi,
-                                                 const uint8_t *Oi, const uint8_t *Ki, const uint8_t *Vi, uint8_t *Pi,
-                                                 uint8_t *Si, int qw0, int row, int key0, float l, float dd, int lane) {
-    const int lg = lane >> 4, lc = lane & 15;
-    f32x4 sc[TK], dp[TK];
-    bwd_block_products(Qi, Oi, Ki, Vi, qw0, lane, sc, dp);
-#pragma unroll
-    for (int j = 0; j < TK; ++j) {
-        const int kb0 = 16 * j + 4 * lg;
-        float pv[4], sv[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float p = __expf(sc[j][r] * a.scale - l);
-            const bool kp = keep_elem(seed, bh, row, key0 + kb0 + r, a.thresh);
-            const float dpd = kp ? dp[j][r] * a.inv_keep : 0.f;
-            pv[r] = kp ? p * a.inv_keep : 0.f;
-            sv[r] = p * (dpd - dd);
-        }
-        if (Pi)
-            *reinterpret_cast<uint2 *>(Pi + off<128>(qw0 + lc, kb0)) = make_uint2(pack_bf16x2_hw(pv[0], pv[1]),
-                                                                                  pack_bf16x2_hw(pv[2], pv[3]));
-        *reinterpret_cast<uint2 *>(Si + off<128>(qw0 + lc, kb0)) = make_uint2(pack_bf16x2_hw(sv[0], sv[1]),
-                                                                              pack_bf16x2_hw(sv[2], sv[3]));
     }
 }
 

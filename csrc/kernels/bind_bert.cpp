@@ -111,24 +111,38 @@ std::tuple<int, int, int> check_qkv(const at::Tensor &qkv, int64_t heads, const 
     return {narrow(qkv.size(0), op, "B"), narrow(qkv.size(1), op, "S"), narrow(heads, op, "heads")};
 }
 
+// The optional per-sequence lengths of a padded batch: contiguous int32 [B] on qkv's device (null when absent).
+// They select the length-aware streaming kernels (attention_lengths.hip), which S = 64 does not have.
+const int *check_lengths(const OptTensor &lengths, const at::Tensor &qkv, const char *op) {
+    if (!has(lengths)) return nullptr;
+    TORCH_CHECK(lengths->scalar_type() == at::kInt && lengths->dim() == 1 && lengths->size(0) == qkv.size(0) &&
+                    lengths->is_contiguous() && lengths->device() == qkv.device(),
+                op, ": lengths must be a contiguous int32 [B] tensor on qkv's device");
+    TORCH_CHECK(qkv.size(1) >= 128, op, ": lengths need S >= 128 (S = 64 has no length-aware kernel)");
+    return lengths->data_ptr<int>();
+}
+
 // Fused self-attention: qkv [B, S, 3*H*64] bf16 contiguous -> (out [B, S, H*64] bf16, lse [B, H, S] f32)
 // stream_kernel: S = 128 on the streaming kernels of attention_long.hip (S > 128 always runs them)
+// lengths: keys and rows at or beyond lengths[b] are padding (zero rows in out, lse = +inf there)
 std::vector<at::Tensor> attention_forward(at::Tensor qkv, int64_t heads, double scale, int64_t seed, double p_drop,
-                                          bool stream_kernel) {
+                                          bool stream_kernel, OptTensor lengths) {
     const auto [B, S, H] = check_qkv(qkv, heads, "attention_forward", stream_kernel);
+    const int *len = check_lengths(lengths, qkv, "attention_forward");
     c10::DeviceGuard gd(qkv.device());
     auto out = at::empty({B, S, H * 64}, qkv.options());
     auto lse = at::empty({B, H, S}, qkv.options().dtype(at::kFloat));
     kfk::launch_attention_forward(bf16(qkv), bf16_mut(out), lse.data_ptr<float>(), B, S, H, static_cast<float>(scale),
                                   static_cast<uint32_t>(seed), static_cast<float>(p_drop), stream_of(qkv, 0),
-                                  stream_kernel);
+                                  stream_kernel, len);
     return {out, lse};
 }
 
 at::Tensor attention_backward(at::Tensor qkv, at::Tensor out, at::Tensor lse, at::Tensor dout, int64_t heads,
-                              double scale, int64_t seed, double p_drop, bool stream_kernel) {
+                              double scale, int64_t seed, double p_drop, bool stream_kernel, OptTensor lengths) {
     const char *op = "attention_backward";
     const auto [B, S, H] = check_qkv(qkv, heads, op, stream_kernel);
+    const int *len = check_lengths(lengths, qkv, op);
     const Dev dev = qkv.device();
     check_dense(out, op, "out", dev, at::kBFloat16, out.numel());
     TORCH_CHECK(out.sizes() == at::IntArrayRef({B, S, H * 64}),
@@ -142,10 +156,11 @@ at::Tensor attention_backward(at::Tensor qkv, at::Tensor out, at::Tensor lse, at
     auto dqkv = at::empty_like(qkv);
     // rowsum(dO o O): the streaming dQ kernel fills it for the dK/dV kernel
     at::Tensor dsum;
-    if (S > 128 || stream_kernel) dsum = at::empty({B, H, S}, lse.options());
+    if (S > 128 || stream_kernel || len) dsum = at::empty({B, H, S}, lse.options());
     kfk::launch_attention_backward(bf16(qkv), bf16(out), lse.data_ptr<float>(), bf16(dout), bf16_mut(dqkv), B, S, H,
                                    static_cast<float>(scale), static_cast<uint32_t>(seed), static_cast<float>(p_drop),
-                                   stream_of(qkv, 0), dsum.defined() ? dsum.data_ptr<float>() : nullptr, stream_kernel);
+                                   stream_of(qkv, 0), dsum.defined() ? dsum.data_ptr<float>() : nullptr, stream_kernel,
+                                   len);
     return dqkv;
 }
 
@@ -316,12 +331,13 @@ void bind_bert(py::module_ &m) {
     m.def("attention_supported", &kfk::attention_supported);
     m.def("attention_forward", &attention_forward,
           "fused self-attention forward (S 64..512 in steps of 64, head dim 64, dropout) -> (out, lse); "
-          "stream_kernel: S = 128 on the streaming kernels that serve S > 128",
+          "stream_kernel: S = 128 on the streaming kernels that serve S > 128; lengths: int32 [B] per-sequence "
+          "lengths of a padded batch (S >= 128), read on the device only",
           py::arg("qkv"), py::arg("heads"), py::arg("scale"), py::arg("seed"), py::arg("p_drop"),
-          py::arg("stream_kernel") = false);
+          py::arg("stream_kernel") = false, py::arg("lengths") = py::none());
     m.def("attention_backward", &attention_backward, "fused self-attention backward -> dqkv (S as the forward)",
           py::arg("qkv"), py::arg("out"), py::arg("lse"), py::arg("dout"), py::arg("heads"), py::arg("scale"),
-          py::arg("seed"), py::arg("p_drop"), py::arg("stream_kernel") = false);
+          py::arg("seed"), py::arg("p_drop"), py::arg("stream_kernel") = false, py::arg("lengths") = py::none());
     m.def("gemm_nt", &gemm_nt, py::arg("a"), py::arg("b"), py::arg("bias") = py::none(), py::arg("out") = py::none(),
           py::arg("accumulate") = false, py::arg("bn") = -1,
           "bf16 a[M,K] . b[N,K]^T (+bias) (+out) on the pipelined 256 x bn MFMA GEMM (gemm.hip)");

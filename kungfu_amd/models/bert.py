@@ -1,8 +1,11 @@
 """BERT-base encoder for masked-LM pre-training throughput (BASELINE.json config 5:
 "BERT-base SynchronousSGD + gradient-noise-scale monitor + elastic resize").
 12 layers, hidden 768, 12 heads, FFN 3072, vocab 30522, ~110 M parameters.
-Attention: the fused HIP kernels of ops/attention.py (S 64 .. 512 in steps of 64, no mask), else
-torch's scaled_dot_product_attention (also for S > 128 with KUNGFU_ATTN_LONG=0)."""
+Attention: the fused HIP kernels of ops/attention.py (S 64 .. 512 in steps of 64), else
+torch's scaled_dot_product_attention (also for S > 128 with KUNGFU_ATTN_LONG=0).  Padded batches pass
+``lengths`` (int32 [B], the valid tokens of each sequence) and stay on the fused kernels from S = 128 up:
+padded rows of the attention output are zero and add nothing to any gradient.  A general ``mask`` still
+takes the scaled_dot_product_attention path; giving both is an error."""
 import math
 
 import torch
@@ -32,7 +35,9 @@ class BertLayer(nn.Module):
         self.ln2 = AddLayerNorm(d, eps=1e-12)
         self.dropout = dropout
 
-    def forward(self, x, mask=None):
+    def forward(self, x, mask=None, lengths=None):
+        if mask is not None and lengths is not None:
+            raise ValueError("BertLayer: give either mask or lengths, not both")
         B, S, D = x.shape
         p = self.dropout if self.training else 0.0
         # x feeds exactly two consumers, the QKV projection and ln1's skip input: ln1's backward hands
@@ -41,7 +46,7 @@ class BertLayer(nn.Module):
         qkv = self.qkv(x)
         if mask is None:
             # fused HIP attention straight from / into the projections' layouts (SDPA off that path)
-            a = self_attention(qkv, self.heads, p)
+            a = self_attention(qkv, self.heads, p) if lengths is None else self_attention(qkv, self.heads, p, lengths)
         else:
             q, k, v = qkv.view(B, S, 3, self.heads, D // self.heads).permute(2, 0, 3, 1, 4)
             a = F.scaled_dot_product_attention(q, k, v, attn_mask=mask, dropout_p=p)
@@ -78,8 +83,9 @@ class BertForPreTraining(nn.Module):
         if isinstance(m, nn.Linear) and m.bias is not None:
             nn.init.zeros_(m.bias)
 
-    def forward(self, ids, types=None, mlm_positions=None):
-        """Returns (MLM logits, NSP logits).  With ``mlm_positions`` ([B, P] token indices,
+    def forward(self, ids, types=None, mlm_positions=None, lengths=None):
+        """Returns (MLM logits, NSP logits).  ``lengths`` (int32 [B] on ``ids``' device): the valid tokens of
+        each padded sequence, handed to every layer's attention.  With ``mlm_positions`` ([B, P] token indices,
         the masked positions: 20 per 128-token sequence in BERT pre-training) only those
         positions go through the MLM head -- the vocabulary projection is the largest GEMM
         of the model, and pre-training never needs it for unmasked tokens."""
@@ -96,7 +102,7 @@ class BertForPreTraining(nn.Module):
             e = e.to(torch.get_autocast_dtype(e.device.type))
         x = self.ln(e)
         for layer in self.layers:
-            x = layer(x)
+            x = layer(x) if lengths is None else layer(x, lengths=lengths)
         hs = x
         if mlm_positions is not None:
             hs = torch.gather(x, 1, mlm_positions.unsqueeze(-1).expand(-1, -1, x.shape[-1]))

@@ -1,6 +1,7 @@
 """Fused multi-head self-attention on the HIP kernels of csrc/kernels/attention.hip (S = 64 or
-128: the whole sequence in LDS) and csrc/kernels/attention_long.hip (S = 192 .. 512 in steps of
-64: a resident row block, streamed column blocks, online softmax).
+128: the whole sequence in LDS), csrc/kernels/attention_long.hip (S = 192 .. 512 in steps of
+64: a resident row block, streamed column blocks, online softmax) and
+csrc/kernels/attention_lengths.hip (padded batches: the streaming kernels with per-sequence lengths).
 
 ``self_attention(qkv, heads, p)`` takes the fused q/k/v projection output ``[B, S, 3*H*64]``
 (the ``[B, S, 3, H, 64]`` layout of one ``nn.Linear(d, 3d)``) and returns the attention output
@@ -10,9 +11,18 @@ gradient (no concatenation).  Dropout on the attention probabilities uses a coun
 (seed, b*H + h, query, key) -- the mask is recomputed in the backward, never stored;
 :func:`dropout_keep` reproduces it in torch for the tests.
 
-Covers BERT's shapes (S a multiple of 64 up to 512 tokens, head dim 64, no attention mask);
-anything else runs ``F.scaled_dot_product_attention``, and so does S > 128 with
-``KUNGFU_ATTN_LONG=0``.
+Padded batches: ``self_attention(qkv, heads, p, lengths)`` with ``lengths`` an int32 ``[B]`` tensor on
+``qkv``'s device (values are clamped to [0, S]).  Sequence ``b`` attends to its first ``lengths[b]`` keys only;
+its rows at or beyond that length come out exactly zero and receive exactly zero dq / dk / dv, and a length of 0
+gives an all-zero sequence (no NaN).  S = 128 .. 512 runs the length-aware streaming kernels, whose block loops stop
+at the length: padding costs nothing there.  ``lengths`` is read on the device only -- no host sync, and a
+captured graph follows a ``lengths`` tensor overwritten in place.  The padded rows of ``qkv`` and of the
+incoming gradient must be finite (they share 64-row blocks with valid rows).
+
+Covers BERT's shapes (S a multiple of 64 up to 512 tokens, head dim 64; no general attention mask, only
+per-sequence lengths); anything else runs ``F.scaled_dot_product_attention``, and so does S > 128 with
+``KUNGFU_ATTN_LONG=0``.  With ``lengths`` the fallback (CPU, f32, S = 64, ``KUNGFU_ATTN_LONG=0``) is a torch
+composition of the same semantics (:func:`_lengths_fallback`).
 """
 from __future__ import annotations
 
@@ -36,34 +46,68 @@ _LONG_ENABLED = os.environ.get("KUNGFU_ATTN_LONG", "1") != "0"
 
 class _AttnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, heads, p, seed):
+    def forward(ctx, qkv, heads, p, seed, lengths=None):
         scale = 1.0 / math.sqrt(64.0)
-        out, lse = hip().attention_forward(qkv, heads, scale, seed, p)
-        ctx.save_for_backward(qkv, out, lse)
+        out, lse = hip().attention_forward(qkv, heads, scale, seed, p, lengths=lengths)
+        ctx.save_for_backward(qkv, out, lse, lengths)  # lse is +inf on the padded rows: the backward's row mask
         ctx.heads, ctx.p, ctx.seed, ctx.scale = heads, p, seed, scale
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        qkv, out, lse = ctx.saved_tensors
-        dqkv = hip().attention_backward(qkv, out, lse, dout.contiguous(), ctx.heads, ctx.scale, ctx.seed, ctx.p)
-        return dqkv, None, None, None
+        qkv, out, lse, lengths = ctx.saved_tensors
+        dqkv = hip().attention_backward(qkv, out, lse, dout.contiguous(), ctx.heads, ctx.scale, ctx.seed, ctx.p,
+                                        lengths=lengths)
+        return dqkv, None, None, None, None
 
 
-def eligible(qkv: torch.Tensor, heads: int) -> bool:
+def eligible(qkv: torch.Tensor, heads: int, lengths=None) -> bool:
+    """Whether the fused kernels serve this call; with ``lengths`` only the streaming family does
+    (S >= 128, and not with ``KUNGFU_ATTN_LONG=0``)."""
     return (qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.dim() == 3 and qkv.is_contiguous()
             and qkv.shape[2] == 3 * heads * 64 and (_LONG_ENABLED or qkv.shape[1] <= 128)
+            and (lengths is None or (_LONG_ENABLED and qkv.shape[1] >= 128))
             and hip_available() and hip().attention_supported(int(qkv.shape[1]), 64))
 
 
-def self_attention(qkv: torch.Tensor, heads: int, p: float = 0.0) -> torch.Tensor:
-    """softmax(Q K^T / sqrt(64)) V with dropout ``p`` on the probabilities, per head;
-    ``qkv``: [B, S, 3*H*dh] -> [B, S, H*dh]."""
+def _check_lengths(qkv: torch.Tensor, lengths: torch.Tensor) -> None:
+    if (lengths.dtype != torch.int32 or lengths.shape != (qkv.shape[0],) or lengths.device != qkv.device
+            or not lengths.is_contiguous()):
+        raise ValueError("self_attention: lengths must be a contiguous int32 [B] tensor on qkv's device, got %s %s "
+                         "(strides %s) on %s" % (lengths.dtype, tuple(lengths.shape), lengths.stride(), lengths.device))
+
+
+def _lengths_fallback(qkv: torch.Tensor, heads: int, p: float, lengths: torch.Tensor) -> torch.Tensor:
+    """The torch composition of the length semantics: keys >= L masked out of the softmax, rows >= L zero.
+    An all-padding sequence (L = 0) would make every softmax row -inf everywhere, hence NaN forward and
+    backward: its scores are left unmasked instead (finite) and its rows are zeroed like any padded row."""
     B, S, D3 = qkv.shape
-    if eligible(qkv, heads):
+    dh = D3 // (3 * heads)
+    q, k, v = qkv.view(B, S, 3, heads, dh).permute(2, 0, 3, 1, 4)
+    L = lengths.clamp(0, S).view(B, 1, 1, 1)
+    valid = torch.arange(S, device=qkv.device).view(1, 1, S) < L.view(B, 1, 1)  # [B, 1, S]
+    s = (q @ k.transpose(-1, -2)) / math.sqrt(dh)
+    s = s.masked_fill(~(valid.view(B, 1, 1, S) | (L == 0)), float("-inf"))
+    a = F.dropout(torch.softmax(s, dim=-1), p) @ v  # [B, H, S, dh]
+    a = a * valid.view(B, 1, S, 1).to(a.dtype)
+    return a.transpose(1, 2).reshape(B, S, heads * dh)
+
+
+def self_attention(qkv: torch.Tensor, heads: int, p: float = 0.0, lengths: torch.Tensor | None = None) -> torch.Tensor:
+    """softmax(Q K^T / sqrt(64)) V with dropout ``p`` on the probabilities, per head;
+    ``qkv``: [B, S, 3*H*dh] -> [B, S, H*dh].  ``lengths`` (int32 [B], on qkv's device): the valid
+    tokens of each padded sequence (module docstring)."""
+    B, S, D3 = qkv.shape
+    if lengths is not None:
+        _check_lengths(qkv, lengths)
+    if eligible(qkv, heads, lengths):
         seed = int(torch.randint(0, 2**31 - 1, (1,)).item())  # CPU generator: no device sync
         dropout_seed.base(qkv.device)  # registers the device seed word (graph replays advance it)
-        return _AttnFn.apply(qkv, heads, float(p), seed)
+        if lengths is None:
+            return _AttnFn.apply(qkv, heads, float(p), seed)
+        return _AttnFn.apply(qkv, heads, float(p), seed, lengths)
+    if lengths is not None:
+        return _lengths_fallback(qkv, heads, p, lengths)
     dh = D3 // (3 * heads)
     q, k, v = qkv.view(B, S, 3, heads, dh).permute(2, 0, 3, 1, 4)
     a = F.scaled_dot_product_attention(q, k, v, dropout_p=p)

@@ -5,7 +5,14 @@ resulting fraction of a 5.3 TB/s streaming roofline.  Next to it the time of wha
 replaces: ``ops.attention.self_attention`` on its SDPA fallback (``KUNGFU_ATTN_LONG=0`` for
 S > 128), head permutes, transposed output copy and dq/dk/dv concatenation included.
 
-    python tools/bench_attention.py [calls] [--batch 128] [--seq 128] [--heads 12]"""
+With ``--lengths`` (a fraction of S in (0, 1]: every sequence that long; or ``random``: seeded uniform
+lengths in [1, S]) it times a padded batch instead, forward + backward per variant, the variants
+alternating over ``--rounds`` rounds in this one process: the fused call without lengths twice (``full``
+and ``full again``: their difference is the run-to-run spread), the length-aware kernels
+(attention_lengths.hip) and the SDPA path a masked batch took before them (BertLayer's: head permutes, a
+boolean key mask, transposed output copy, dq/dk/dv concatenation).
+
+    python tools/bench_attention.py [calls] [--batch 128] [--seq 128] [--heads 12] [--lengths 0.5|random]"""
 import argparse
 import os
 import sys
@@ -47,12 +54,66 @@ def sdpa_fallback(qkv, dout, NH, p, n):
     return tf, tb
 
 
+def sdpa_mask_fns(qkv, dout, NH, p, lengths):
+    """(forward, backward) closures of BertLayer's mask path for the key mask of ``lengths``."""
+    B, S, D3 = qkv.shape
+    mask = (torch.arange(S, device=qkv.device).view(1, 1, 1, S) < lengths.view(B, 1, 1, 1))
+    q = qkv.clone().requires_grad_(True)
+
+    def fwd():
+        qq, k, v = q.view(B, S, 3, NH, 64).permute(2, 0, 3, 1, 4)
+        a = torch.nn.functional.scaled_dot_product_attention(qq, k, v, attn_mask=mask, dropout_p=p)
+        return a.transpose(1, 2).reshape(B, S, NH * 64)
+
+    y = fwd()
+    return fwd, lambda: torch.autograd.grad(y, q, dout, retain_graph=True)
+
+
+def padded(args, H, qkv, dout, scale):
+    """Forward + backward time per variant on a padded batch, the variants alternating over the rounds."""
+    B, S, NH = args.batch, args.seq, args.heads
+    if args.lengths == "random":
+        g = torch.Generator().manual_seed(args.seed)
+        lengths = torch.randint(1, S + 1, (B,), generator=g, dtype=torch.int32).cuda()
+    else:
+        lengths = torch.full((B,), max(1, min(S, round(float(args.lengths) * S))), dtype=torch.int32, device="cuda")
+    print("lengths %s: mean %.1f of %d tokens (%.0f %% valid)" % (
+        args.lengths, lengths.float().mean().item(), S, 100 * lengths.float().mean().item() / S), flush=True)
+    for p in (0.1, 0.0):
+        out, lse = H.attention_forward(qkv, NH, scale, 1234, p)
+        lout, llse = H.attention_forward(qkv, NH, scale, 1234, p, lengths=lengths)
+        sf, sb = sdpa_mask_fns(qkv, dout, NH, p, lengths)
+        full = (lambda: H.attention_forward(qkv, NH, scale, 1234, p),
+                lambda: H.attention_backward(qkv, out, lse, dout, NH, scale, 1234, p))
+        variants = {
+            "full": full, "full again": full,
+            "lengths": (lambda: H.attention_forward(qkv, NH, scale, 1234, p, lengths=lengths),
+                        lambda: H.attention_backward(qkv, lout, llse, dout, NH, scale, 1234, p, lengths=lengths)),
+            "sdpa mask": (sf, sb)}
+        ts = {k: [] for k in variants}
+        for _ in range(args.rounds):
+            for k, (f, b) in variants.items():
+                ts[k].append((med(f, args.calls), med(b, args.calls)))
+        m = {}
+        for k, v in ts.items():
+            tot = sorted(f + b for f, b in v)
+            m[k] = tot[len(tot) // 2]
+            print("p=%.1f  %-10s fwd %7.1f us  bwd %7.1f us  fwd+bwd median %7.1f us (min %7.1f max %7.1f over %d rounds)" % (
+                p, k, sorted(f for f, _ in v)[len(v) // 2], sorted(b for _, b in v)[len(v) // 2], m[k], tot[0], tot[-1],
+                len(v)), flush=True)
+        print("p=%.1f  full again / full %.3f   lengths / full %.3f   lengths / sdpa mask %.3f" % (
+            p, m["full again"] / m["full"], m["lengths"] / m["full"], m["lengths"] / m["sdpa mask"]), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("calls", nargs="?", type=int, default=20, help="calls to time")
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--seq", type=int, default=128)
     ap.add_argument("--heads", type=int, default=12)
+    ap.add_argument("--lengths", default=None, help="padded batch: a fraction of S in (0, 1], or 'random'")
+    ap.add_argument("--rounds", type=int, default=5, help="--lengths: rounds the variants alternate over")
+    ap.add_argument("--seed", type=int, default=0, help="--lengths random: seed of the lengths")
     args = ap.parse_args()
     n = args.calls
     H = hip()
@@ -63,6 +124,8 @@ def main():
     dout = (torch.randn(B, S, D, device="cuda") * 0.1).bfloat16()
     scale = 64 ** -0.5
     print("B=%d S=%d H=%d" % (B, S, NH), flush=True)
+    if args.lengths is not None:
+        return padded(args, H, qkv, dout, scale)
     for p in (0.1, 0.0):
         out, lse = H.attention_forward(qkv, NH, scale, 1234, p)
         tf = med(lambda: H.attention_forward(qkv, NH, scale, 1234, p), n)
