@@ -327,12 +327,20 @@ static void check_length(int S, bool stream_kernel) {
         throw std::invalid_argument("attention: stream_kernel needs S >= 128");
 }
 
+static constexpr const char *kCausalLengths =
+    "attention: causal attention takes no lengths: right padding cannot reach a valid row";
+
 bool attention_supported(int S, int head_dim) {
     return head_dim == DH && (whole_sequence(S) || (S > 128 && attention_long_supported(S)));
 }
 
 void launch_attention_forward(const uint16_t *qkv, uint16_t *out, float *lse, int B, int S, int H, float scale,
-                              uint32_t seed, float p_drop, hipStream_t s, bool stream_kernel, const int *lengths) {
+                              uint32_t seed, float p_drop, hipStream_t s, bool stream_kernel, const int *lengths,
+                              bool causal, bool plain_order) {
+    if (causal) {
+        if (lengths) throw std::invalid_argument(kCausalLengths);
+        return launch_attention_causal_forward(qkv, out, lse, B, S, H, scale, seed, p_drop, s, plain_order);
+    }
     check_length(S, stream_kernel);
     if (lengths) return launch_attention_lengths_forward(qkv, out, lse, lengths, B, S, H, scale, seed, p_drop, s);
     if (!whole_sequence(S) || stream_kernel)
@@ -344,7 +352,13 @@ void launch_attention_forward(const uint16_t *qkv, uint16_t *out, float *lse, in
 
 void launch_attention_backward(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *dout,
                                uint16_t *dqkv, int B, int S, int H, float scale, uint32_t seed, float p_drop,
-                               hipStream_t s, float *dsum, bool stream_kernel, const int *lengths) {
+                               hipStream_t s, float *dsum, bool stream_kernel, const int *lengths, bool causal,
+                               bool plain_order) {
+    if (causal) {
+        if (lengths) throw std::invalid_argument(kCausalLengths);
+        return launch_attention_causal_backward(qkv, out, lse, dout, dqkv, dsum, B, S, H, scale, seed, p_drop, s,
+                                                plain_order);
+    }
     check_length(S, stream_kernel);
     if (lengths)
         return launch_attention_lengths_backward(qkv, out, lse, dout, dqkv, dsum, lengths, B, S, H, scale, seed, p_drop, s);

@@ -1,5 +1,5 @@
 // Device helpers shared by the fused attention kernels (attention.hip: whole sequence in LDS,
-// attention_long.hip and attention_lengths.hip: streamed blocks): the swizzled LDS image addressing, the MFMA operand
+// attention_long.hip, attention_lengths.hip and attention_causal.hip: streamed blocks): the swizzled LDS image addressing, the MFMA operand
 // fragments, the dropout hash, the LDS-DMA staging and the kernel argument block.  Private to
 // those files: everything sits in an unnamed namespace.
 #pragma once
@@ -122,5 +122,13 @@ void launch_attention_lengths_forward(const uint16_t *qkv, uint16_t *out, float 
 void launch_attention_lengths_backward(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *dout,
                                        uint16_t *dqkv, float *dsum, const int *lengths, int B, int S, int H,
                                        float scale, uint32_t seed, float p_drop, hipStream_t s);
+// attention_causal.hip: the causal members of the family (query q sees keys <= q), every multiple of 64 from 64 to
+// 1024 (attention_causal_supported, kernels.hpp); plain_order: the workgroup order of the kernels above instead of
+// heaviest-first (for measurements)
+void launch_attention_causal_forward(const uint16_t *qkv, uint16_t *out, float *lse, int B, int S, int H, float scale,
+                                     uint32_t seed, float p_drop, hipStream_t s, bool plain_order = false);
+void launch_attention_causal_backward(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *dout,
+                                      uint16_t *dqkv, float *dsum, int B, int S, int H, float scale, uint32_t seed,
+                                      float p_drop, hipStream_t s, bool plain_order = false);
 
 }  // namespace kfk

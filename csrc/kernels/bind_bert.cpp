@@ -101,10 +101,20 @@ at::Tensor colsum(at::Tensor x, at::ScalarType dtype) {
     return out;
 }
 
+constexpr const char *kCausalLengths = "causal attention takes no lengths: right padding cannot reach a valid row";
+
 // contiguous bf16 [B, S, 3*H*64] with S a multiple of 64 up to 512: {B, S, H}
 // (stream_kernel, the streaming kernels at S = 128 for tests, is refused where they do not exist: S = 64)
-std::tuple<int, int, int> check_qkv(const at::Tensor &qkv, int64_t heads, const char *op, bool stream_kernel) {
+// causal: S a multiple of 64 up to 1024 (attention_causal.hip); stream_kernel is ignored there
+std::tuple<int, int, int> check_qkv(const at::Tensor &qkv, int64_t heads, const char *op, bool stream_kernel,
+                                    bool causal = false) {
     check_dense(qkv, op, "qkv", kAnyGpu, at::kBFloat16, qkv.numel());
+    if (causal) {
+        TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == 3 * heads * 64 && qkv.size(1) <= 1024 &&
+                        kfk::attention_causal_supported(static_cast<int>(qkv.size(1))),
+                    op, ": causal qkv must be [B, S, 3*H*64] with S a multiple of 64 from 64 to 1024");
+        return {narrow(qkv.size(0), op, "B"), narrow(qkv.size(1), op, "S"), narrow(heads, op, "heads")};
+    }
     TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == 3 * heads * 64 && kfk::attention_supported(qkv.size(1), 64), op,
                 ": qkv must be [B, S, 3*H*64] with S ", kfk::kAttentionLengths);
     TORCH_CHECK(!stream_kernel || qkv.size(1) >= 128, op, ": stream_kernel needs S >= 128");
@@ -126,22 +136,25 @@ const int *check_lengths(const OptTensor &lengths, const at::Tensor &qkv, const 
 // stream_kernel: S = 128 on the streaming kernels of attention_long.hip (S > 128 always runs them)
 // lengths: keys and rows at or beyond lengths[b] are padding (zero rows in out, lse = +inf there)
 std::vector<at::Tensor> attention_forward(at::Tensor qkv, int64_t heads, double scale, int64_t seed, double p_drop,
-                                          bool stream_kernel, OptTensor lengths) {
-    const auto [B, S, H] = check_qkv(qkv, heads, "attention_forward", stream_kernel);
+                                          bool stream_kernel, OptTensor lengths, bool causal, bool plain_order) {
+    TORCH_CHECK(!(causal && has(lengths)), "attention_forward: ", kCausalLengths);
+    const auto [B, S, H] = check_qkv(qkv, heads, "attention_forward", stream_kernel, causal);
     const int *len = check_lengths(lengths, qkv, "attention_forward");
     c10::DeviceGuard gd(qkv.device());
     auto out = at::empty({B, S, H * 64}, qkv.options());
     auto lse = at::empty({B, H, S}, qkv.options().dtype(at::kFloat));
     kfk::launch_attention_forward(bf16(qkv), bf16_mut(out), lse.data_ptr<float>(), B, S, H, static_cast<float>(scale),
                                   static_cast<uint32_t>(seed), static_cast<float>(p_drop), stream_of(qkv, 0),
-                                  stream_kernel, len);
+                                  stream_kernel, len, causal, plain_order);
     return {out, lse};
 }
 
 at::Tensor attention_backward(at::Tensor qkv, at::Tensor out, at::Tensor lse, at::Tensor dout, int64_t heads,
-                              double scale, int64_t seed, double p_drop, bool stream_kernel, OptTensor lengths) {
+                              double scale, int64_t seed, double p_drop, bool stream_kernel, OptTensor lengths,
+                              bool causal, bool plain_order) {
     const char *op = "attention_backward";
-    const auto [B, S, H] = check_qkv(qkv, heads, op, stream_kernel);
+    TORCH_CHECK(!(causal && has(lengths)), op, ": ", kCausalLengths);
+    const auto [B, S, H] = check_qkv(qkv, heads, op, stream_kernel, causal);
     const int *len = check_lengths(lengths, qkv, op);
     const Dev dev = qkv.device();
     check_dense(out, op, "out", dev, at::kBFloat16, out.numel());
@@ -156,11 +169,11 @@ at::Tensor attention_backward(at::Tensor qkv, at::Tensor out, at::Tensor lse, at
     auto dqkv = at::empty_like(qkv);
     // rowsum(dO o O): the streaming dQ kernel fills it for the dK/dV kernel
     at::Tensor dsum;
-    if (S > 128 || stream_kernel || len) dsum = at::empty({B, H, S}, lse.options());
+    if (S > 128 || stream_kernel || len || causal) dsum = at::empty({B, H, S}, lse.options());
     kfk::launch_attention_backward(bf16(qkv), bf16(out), lse.data_ptr<float>(), bf16(dout), bf16_mut(dqkv), B, S, H,
                                    static_cast<float>(scale), static_cast<uint32_t>(seed), static_cast<float>(p_drop),
                                    stream_of(qkv, 0), dsum.defined() ? dsum.data_ptr<float>() : nullptr, stream_kernel,
-                                   len);
+                                   len, causal, plain_order);
     return dqkv;
 }
 
@@ -329,15 +342,19 @@ void bind_bert(py::module_ &m) {
           py::arg("s"), py::arg("gamma"), py::arg("mean"), py::arg("rstd"), py::arg("p") = 0.0, py::arg("seed") = 0,
           py::arg("rbias_dtype") = py::none());
     m.def("attention_supported", &kfk::attention_supported);
+    m.def("attention_causal_supported", &kfk::attention_causal_supported);
     m.def("attention_forward", &attention_forward,
           "fused self-attention forward (S 64..512 in steps of 64, head dim 64, dropout) -> (out, lse); "
           "stream_kernel: S = 128 on the streaming kernels that serve S > 128; lengths: int32 [B] per-sequence "
-          "lengths of a padded batch (S >= 128), read on the device only",
+          "lengths of a padded batch (S >= 128), read on the device only; causal: query q sees keys <= q (S 64..1024 "
+          "in steps of 64, no lengths, stream_kernel ignored); plain_order: the causal workgroups not heaviest-first",
           py::arg("qkv"), py::arg("heads"), py::arg("scale"), py::arg("seed"), py::arg("p_drop"),
-          py::arg("stream_kernel") = false, py::arg("lengths") = py::none());
+          py::arg("stream_kernel") = false, py::arg("lengths") = py::none(), py::arg("causal") = false,
+          py::arg("plain_order") = false);
     m.def("attention_backward", &attention_backward, "fused self-attention backward -> dqkv (S as the forward)",
           py::arg("qkv"), py::arg("out"), py::arg("lse"), py::arg("dout"), py::arg("heads"), py::arg("scale"),
-          py::arg("seed"), py::arg("p_drop"), py::arg("stream_kernel") = false, py::arg("lengths") = py::none());
+          py::arg("seed"), py::arg("p_drop"), py::arg("stream_kernel") = false, py::arg("lengths") = py::none(),
+          py::arg("causal") = false, py::arg("plain_order") = false);
     m.def("gemm_nt", &gemm_nt, py::arg("a"), py::arg("b"), py::arg("bias") = py::none(), py::arg("out") = py::none(),
           py::arg("accumulate") = false, py::arg("bn") = -1,
           "bf16 a[M,K] . b[N,K]^T (+bias) (+out) on the pipelined 256 x bn MFMA GEMM (gemm.hip)");

@@ -509,16 +509,20 @@ void launch_maxpool2x2_backward(const uint16_t *x, const uint16_t *dy, uint16_t 
 // lengths (int32 [B] on the device, or null): sequence b attends to its first lengths[b] keys only, and its
 // rows beyond that get zero out / dq / dk / dv -- the length-aware streaming kernels of attention_lengths.hip,
 // S = 128 .. 512 (refused at S = 64); read by the kernels only, no host sync.
+// causal: query q attends to keys <= q -- the triangular streaming kernels of attention_causal.hip, every multiple of
+// 64 from 64 to 1024 (attention_causal_supported); takes no lengths, ignores stream_kernel, always needs dsum;
+// plain_order: those kernels' workgroups in the bidirectional kernels' order instead of heaviest-first (measurements).
 bool attention_supported(int S, int head_dim);
+bool attention_causal_supported(int S);
 constexpr const char *kAttentionLengths = "64, 128, 192, 256, 320, 384, 448 or 512";  // the one spelling of the set
 void launch_attention_forward(const uint16_t *qkv, uint16_t *out, float *lse, int B, int S, int H, float scale,
                               uint32_t seed, float p_drop, hipStream_t s, bool stream_kernel = false,
-                              const int *lengths = nullptr);
+                              const int *lengths = nullptr, bool causal = false, bool plain_order = false);
 // dqkv [B, S, 3, H, 64] (every element written); dsum: [B, H, S] f32 scratch, needed (and only
 // touched) by the streaming kernels
 void launch_attention_backward(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *dout,
                                uint16_t *dqkv, int B, int S, int H, float scale, uint32_t seed, float p_drop,
                                hipStream_t s, float *dsum = nullptr, bool stream_kernel = false,
-                               const int *lengths = nullptr);
+                               const int *lengths = nullptr, bool causal = false, bool plain_order = false);
 
 }  // namespace kfk

@@ -10,7 +10,7 @@ def get_model(name: str, **kw):
         "resnet50": ("resnet", "resnet50"), "resnet101": ("resnet", "resnet101"),
         "resnet152": ("resnet", "resnet152"), "vgg16": ("vgg", "vgg16"),
         "inception_v3": ("inception", "inception_v3"), "bert_base": ("bert", "bert_base"),
-        "slp": ("slp", "SLP"),
+        "slp": ("slp", "SLP"), "gpt_base": ("gpt", "gpt_base"),
     }
     mod, fn = table[name]
     return getattr(importlib.import_module("kungfu_amd.models." + mod), fn)(**kw)

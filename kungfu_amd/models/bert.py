@@ -5,7 +5,8 @@ Attention: the fused HIP kernels of ops/attention.py (S 64 .. 512 in steps of 64
 torch's scaled_dot_product_attention (also for S > 128 with KUNGFU_ATTN_LONG=0).  Padded batches pass
 ``lengths`` (int32 [B], the valid tokens of each sequence) and stay on the fused kernels from S = 128 up:
 padded rows of the attention output are zero and add nothing to any gradient.  A general ``mask`` still
-takes the scaled_dot_product_attention path; giving both is an error."""
+takes the scaled_dot_product_attention path; giving both is an error.  ``BertLayer(x, causal=True)`` is the
+decoder block of models/gpt.py: the causal fused kernels, with neither mask nor lengths."""
 import math
 
 import torch
@@ -35,16 +36,20 @@ class BertLayer(nn.Module):
         self.ln2 = AddLayerNorm(d, eps=1e-12)
         self.dropout = dropout
 
-    def forward(self, x, mask=None, lengths=None):
+    def forward(self, x, mask=None, lengths=None, causal=False):
         if mask is not None and lengths is not None:
             raise ValueError("BertLayer: give either mask or lengths, not both")
+        if causal and (mask is not None or lengths is not None):
+            raise ValueError("BertLayer: causal takes neither mask nor lengths")
         B, S, D = x.shape
         p = self.dropout if self.training else 0.0
         # x feeds exactly two consumers, the QKV projection and ln1's skip input: ln1's backward hands
         # its gradient of x to the projection's data-gradient GEMM (ops.linear.ResidualLink)
         residual_link(x)
         qkv = self.qkv(x)
-        if mask is None:
+        if causal:  # the triangular kernels of attention_causal.hip (GPT, models/gpt.py)
+            a = self_attention(qkv, self.heads, p, causal=True)
+        elif mask is None:
             # fused HIP attention straight from / into the projections' layouts (SDPA off that path)
             a = self_attention(qkv, self.heads, p) if lengths is None else self_attention(qkv, self.heads, p, lengths)
         else:

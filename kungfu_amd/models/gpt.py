@@ -1,0 +1,60 @@
+"""GPT (the 2018 decoder-only Transformer language model): 12 post-LN layers, hidden 768, 12 heads of 64,
+FFN 3072, GELU, learned positions, a context of 512 tokens, vocab 40478, tied output embedding, ~116 M
+parameters.  Architecturally BERT's encoder layer with a causal mask: the layers are ``BertLayer``s called
+with ``causal=True``, whose attention runs the triangular fused HIP kernels of ops/attention.py (S a multiple
+of 64 up to 1024; anything else ``F.scaled_dot_product_attention(is_causal=True)``)."""
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from ..ops.embedding import embedding
+from ..ops.vocab import vocab_projection
+from ..ops.xent import cross_entropy
+from .bert import BertLayer
+
+
+class GPTLM(nn.Module):
+    def __init__(self, vocab=40478, d=768, layers=12, heads=12, ffn=3072, max_pos=512, dropout=0.1):
+        super().__init__()
+        self.tok = nn.Embedding(vocab, d)
+        self.pos = nn.Embedding(max_pos, d)
+        self.layers = nn.ModuleList([BertLayer(d, heads, ffn, dropout) for _ in range(layers)])
+        self.dropout = dropout
+        self.apply(self._init)
+
+    @staticmethod
+    def _init(m):
+        if isinstance(m, (nn.Linear, nn.Embedding)):
+            nn.init.normal_(m.weight, std=0.02)
+        if isinstance(m, nn.Linear) and m.bias is not None:
+            nn.init.zeros_(m.bias)
+
+    def forward(self, ids):
+        """Next-token logits [B, S, vocab] of token ids [B, S] (S <= max_pos)."""
+        B, S = ids.shape
+        pos = torch.arange(S, device=ids.device)
+        # scatter-add embedding gradients (ops/embedding.py): fixed-shape, graph-replayable
+        x = embedding(ids, self.tok.weight) + embedding(pos, self.pos.weight)[None]
+        if torch.is_autocast_enabled(x.device.type) and x.is_cuda:
+            x = x.to(torch.get_autocast_dtype(x.device.type))  # bf16 residual stream from here on, as in BERT
+        x = F.dropout(x, self.dropout, self.training)
+        for layer in self.layers:
+            x = layer(x, causal=True)
+        # tied output embedding, no bias; gemm.hip's ragged-N GEMM with padded logits rows (ops/vocab.py)
+        return vocab_projection(x, self.tok.weight)
+
+
+def gpt_base(**kw):
+    kw.pop("fused_bn", None)
+    return GPTLM(**kw)
+
+
+def synthetic_lm_batch(batch: int, seq_len: int = 512, vocab: int = 40478, device=None, generator=None):
+    """Random token ids [batch, seq_len] of a language-model batch."""
+    return torch.randint(0, vocab, (batch, seq_len), device=device, generator=generator)
+
+
+def lm_loss(model, ids):
+    """Mean next-token cross-entropy: positions 0 .. S-2 predict ids[:, 1:] (ops/xent.py on bf16 logits)."""
+    logits = model(ids)
+    return cross_entropy(logits[:, :-1], ids[:, 1:])

@@ -1,7 +1,8 @@
 """Fused multi-head self-attention on the HIP kernels of csrc/kernels/attention.hip (S = 64 or
 128: the whole sequence in LDS), csrc/kernels/attention_long.hip (S = 192 .. 512 in steps of
-64: a resident row block, streamed column blocks, online softmax) and
-csrc/kernels/attention_lengths.hip (padded batches: the streaming kernels with per-sequence lengths).
+64: a resident row block, streamed column blocks, online softmax),
+csrc/kernels/attention_lengths.hip (padded batches: the streaming kernels with per-sequence lengths) and
+csrc/kernels/attention_causal.hip (causal: the streaming kernels with triangular trip counts, S up to 1024).
 
 ``self_attention(qkv, heads, p)`` takes the fused q/k/v projection output ``[B, S, 3*H*64]``
 (the ``[B, S, 3, H, 64]`` layout of one ``nn.Linear(d, 3d)``) and returns the attention output
@@ -23,6 +24,14 @@ Covers BERT's shapes (S a multiple of 64 up to 512 tokens, head dim 64; no gener
 per-sequence lengths); anything else runs ``F.scaled_dot_product_attention``, and so does S > 128 with
 ``KUNGFU_ATTN_LONG=0``.  With ``lengths`` the fallback (CPU, f32, S = 64, ``KUNGFU_ATTN_LONG=0``) is a torch
 composition of the same semantics (:func:`_lengths_fallback`).
+
+Causal (decoder) attention: ``self_attention(qkv, heads, p, causal=True)`` -- query ``q`` attends to keys ``k <= q``.
+Every S that is a multiple of 64 from 64 to 1024 runs the triangular streaming kernels of
+csrc/kernels/attention_causal.hip: query block ``i`` streams key blocks ``0 .. i`` only and just the diagonal block
+is masked, so about half of the bidirectional call's work is never issued (profiles/attention_causal.md).  Same
+layouts, same dropout hash, bitwise reproducible.  ``causal`` with ``lengths`` is a ``ValueError``: right padding
+cannot influence a valid causal row, so masking the loss is enough.  The fallback (CPU, f32, any other S, and
+S > 128 with ``KUNGFU_ATTN_LONG=0``) is ``F.scaled_dot_product_attention(..., is_causal=True)``.
 """
 from __future__ import annotations
 
@@ -46,24 +55,32 @@ _LONG_ENABLED = os.environ.get("KUNGFU_ATTN_LONG", "1") != "0"
 
 class _AttnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, heads, p, seed, lengths=None):
+    def forward(ctx, qkv, heads, p, seed, lengths=None, causal=False):
         scale = 1.0 / math.sqrt(64.0)
-        out, lse = hip().attention_forward(qkv, heads, scale, seed, p, lengths=lengths)
+        if causal:  # (the keyword is passed only here: calls without it stay what they were)
+            out, lse = hip().attention_forward(qkv, heads, scale, seed, p, causal=True)
+        else:
+            out, lse = hip().attention_forward(qkv, heads, scale, seed, p, lengths=lengths)
         ctx.save_for_backward(qkv, out, lse, lengths)  # lse is +inf on the padded rows: the backward's row mask
-        ctx.heads, ctx.p, ctx.seed, ctx.scale = heads, p, seed, scale
+        ctx.heads, ctx.p, ctx.seed, ctx.scale, ctx.causal = heads, p, seed, scale, causal
         return out
 
     @staticmethod
     def backward(ctx, dout):
         qkv, out, lse, lengths = ctx.saved_tensors
-        dqkv = hip().attention_backward(qkv, out, lse, dout.contiguous(), ctx.heads, ctx.scale, ctx.seed, ctx.p,
-                                        lengths=lengths)
-        return dqkv, None, None, None, None
+        kw = dict(causal=True) if ctx.causal else dict(lengths=lengths)
+        dqkv = hip().attention_backward(qkv, out, lse, dout.contiguous(), ctx.heads, ctx.scale, ctx.seed, ctx.p, **kw)
+        return dqkv, None, None, None, None, None
 
 
-def eligible(qkv: torch.Tensor, heads: int, lengths=None) -> bool:
+def eligible(qkv: torch.Tensor, heads: int, lengths=None, causal: bool = False) -> bool:
     """Whether the fused kernels serve this call; with ``lengths`` only the streaming family does
-    (S >= 128, and not with ``KUNGFU_ATTN_LONG=0``)."""
+    (S >= 128, and not with ``KUNGFU_ATTN_LONG=0``); ``causal``: S a multiple of 64 up to 1024, no lengths."""
+    if causal:
+        return (lengths is None and qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.dim() == 3
+                and qkv.is_contiguous() and qkv.shape[2] == 3 * heads * 64 and qkv.shape[1] <= 1024
+                and (_LONG_ENABLED or qkv.shape[1] <= 128)
+                and hip_available() and hip().attention_causal_supported(int(qkv.shape[1])))
     return (qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.dim() == 3 and qkv.is_contiguous()
             and qkv.shape[2] == 3 * heads * 64 and (_LONG_ENABLED or qkv.shape[1] <= 128)
             and (lengths is None or (_LONG_ENABLED and qkv.shape[1] >= 128))
@@ -93,16 +110,21 @@ def _lengths_fallback(qkv: torch.Tensor, heads: int, p: float, lengths: torch.Te
     return a.transpose(1, 2).reshape(B, S, heads * dh)
 
 
-def self_attention(qkv: torch.Tensor, heads: int, p: float = 0.0, lengths: torch.Tensor | None = None) -> torch.Tensor:
+def self_attention(qkv: torch.Tensor, heads: int, p: float = 0.0, lengths: torch.Tensor | None = None,
+                   causal: bool = False) -> torch.Tensor:
     """softmax(Q K^T / sqrt(64)) V with dropout ``p`` on the probabilities, per head;
     ``qkv``: [B, S, 3*H*dh] -> [B, S, H*dh].  ``lengths`` (int32 [B], on qkv's device): the valid
-    tokens of each padded sequence (module docstring)."""
+    tokens of each padded sequence; ``causal``: query q attends to keys <= q (module docstring)."""
     B, S, D3 = qkv.shape
+    if causal and lengths is not None:
+        raise ValueError("self_attention: causal attention takes no lengths: right padding cannot reach a valid row")
     if lengths is not None:
         _check_lengths(qkv, lengths)
-    if eligible(qkv, heads, lengths):
+    if eligible(qkv, heads, lengths, causal):
         seed = int(torch.randint(0, 2**31 - 1, (1,)).item())  # CPU generator: no device sync
         dropout_seed.base(qkv.device)  # registers the device seed word (graph replays advance it)
+        if causal:
+            return _AttnFn.apply(qkv, heads, float(p), seed, None, True)
         if lengths is None:
             return _AttnFn.apply(qkv, heads, float(p), seed)
         return _AttnFn.apply(qkv, heads, float(p), seed, lengths)
@@ -110,7 +132,7 @@ def self_attention(qkv: torch.Tensor, heads: int, p: float = 0.0, lengths: torch
         return _lengths_fallback(qkv, heads, p, lengths)
     dh = D3 // (3 * heads)
     q, k, v = qkv.view(B, S, 3, heads, dh).permute(2, 0, 3, 1, 4)
-    a = F.scaled_dot_product_attention(q, k, v, dropout_p=p)
+    a = F.scaled_dot_product_attention(q, k, v, dropout_p=p, is_causal=causal)
     return a.transpose(1, 2).reshape(B, S, heads * dh)
 
 

@@ -12,7 +12,12 @@ and ``full again``: their difference is the run-to-run spread), the length-aware
 (attention_lengths.hip) and the SDPA path a masked batch took before them (BertLayer's: head permutes, a
 boolean key mask, transposed output copy, dq/dk/dv concatenation).
 
-    python tools/bench_attention.py [calls] [--batch 128] [--seq 128] [--heads 12] [--lengths 0.5|random]"""
+With ``--causal`` it times the causal kernels (attention_causal.hip), forward and backward separately, the variants
+alternating the same way: the causal call in its heaviest-first workgroup order and in the plain order, the
+bidirectional call at the same shape twice (S <= 512) and the SDPA ``is_causal=True`` path with BertLayer's permutes
+and copies.
+
+    python tools/bench_attention.py [calls] [--batch 128] [--seq 128] [--heads 12] [--lengths 0.5|random] [--causal]"""
 import argparse
 import os
 import sys
@@ -105,6 +110,52 @@ def padded(args, H, qkv, dout, scale):
             p, m["full again"] / m["full"], m["lengths"] / m["full"], m["lengths"] / m["sdpa mask"]), flush=True)
 
 
+def causal(args, H, qkv, dout, scale):
+    """Forward and backward time per variant of a causal call, the variants alternating over the rounds."""
+    B, S, NH = args.batch, args.seq, args.heads
+    n = S // 64
+    print("causal: block steps (n + 1) / 2n of the bidirectional call = %.3f" % ((n + 1) / (2 * n)), flush=True)
+    for p in (0.1, 0.0):
+        cout, clse = H.attention_forward(qkv, NH, scale, 1234, p, causal=True)
+        q = qkv.clone().requires_grad_(True)
+
+        def sdpa_fwd():
+            qq, k, v = q.view(B, S, 3, NH, 64).permute(2, 0, 3, 1, 4)
+            a = torch.nn.functional.scaled_dot_product_attention(qq, k, v, dropout_p=p, is_causal=True)
+            return a.transpose(1, 2).reshape(B, S, NH * 64)
+
+        y = sdpa_fwd()
+        variants = {}
+        for name, plain in (("causal", False), ("causal plain", True)):
+            variants[name] = (
+                lambda plain=plain: H.attention_forward(qkv, NH, scale, 1234, p, causal=True, plain_order=plain),
+                lambda plain=plain: H.attention_backward(qkv, cout, clse, dout, NH, scale, 1234, p, causal=True,
+                                                         plain_order=plain))
+        if H.attention_supported(S, 64):  # the bidirectional kernels stop at S = 512
+            out, lse = H.attention_forward(qkv, NH, scale, 1234, p)
+            variants["full"] = variants["full again"] = (
+                lambda: H.attention_forward(qkv, NH, scale, 1234, p),
+                lambda: H.attention_backward(qkv, out, lse, dout, NH, scale, 1234, p))
+        variants["sdpa causal"] = (sdpa_fwd, lambda: torch.autograd.grad(y, q, dout, retain_graph=True))
+        ts = {k: [] for k in variants}
+        for _ in range(args.rounds):
+            for k, (f, b) in variants.items():
+                ts[k].append((med(f, args.calls), med(b, args.calls)))
+        m = {}
+        for k, v in ts.items():
+            fs, bs = sorted(f for f, _ in v), sorted(b for _, b in v)
+            m[k] = (fs[len(fs) // 2], bs[len(bs) // 2])
+            print("p=%.1f  %-12s fwd %7.1f us (min %7.1f max %7.1f)  bwd %7.1f us (min %7.1f max %7.1f) over %d rounds" % (
+                p, k, m[k][0], fs[0], fs[-1], m[k][1], bs[0], bs[-1], len(v)), flush=True)
+        for i, d in enumerate(("fwd", "bwd")):
+            c = m["causal"][i]
+            line = "p=%.1f  %s: causal / plain order %.3f   causal / sdpa causal %.3f" % (
+                p, d, c / m["causal plain"][i], c / m["sdpa causal"][i])
+            if "full" in m:
+                line += "   causal / full %.3f   full again / full %.3f" % (c / m["full"][i], m["full again"][i] / m["full"][i])
+            print(line, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("calls", nargs="?", type=int, default=20, help="calls to time")
@@ -112,7 +163,8 @@ def main():
     ap.add_argument("--seq", type=int, default=128)
     ap.add_argument("--heads", type=int, default=12)
     ap.add_argument("--lengths", default=None, help="padded batch: a fraction of S in (0, 1], or 'random'")
-    ap.add_argument("--rounds", type=int, default=5, help="--lengths: rounds the variants alternate over")
+    ap.add_argument("--causal", action="store_true", help="causal attention: the triangular kernels and what they replace")
+    ap.add_argument("--rounds", type=int, default=5, help="--lengths / --causal: rounds the variants alternate over")
     ap.add_argument("--seed", type=int, default=0, help="--lengths random: seed of the lengths")
     args = ap.parse_args()
     n = args.calls
@@ -124,6 +176,8 @@ def main():
     dout = (torch.randn(B, S, D, device="cuda") * 0.1).bfloat16()
     scale = 64 ** -0.5
     print("B=%d S=%d H=%d" % (B, S, NH), flush=True)
+    if args.causal:
+        return causal(args, H, qkv, dout, scale)
     if args.lengths is not None:
         return padded(args, H, qkv, dout, scale)
     for p in (0.1, 0.0):
