@@ -177,6 +177,53 @@ at::Tensor attention_backward(at::Tensor qkv, at::Tensor out, at::Tensor lse, at
     return dqkv;
 }
 
+// Head dim 128 (attention_d128.hip): contiguous bf16 [B, S, 3*H*128] with S a multiple of 64 up to 1024: {B, S, H}
+std::tuple<int, int, int> check_qkv_d128(const at::Tensor &qkv, int64_t heads, const char *op) {
+    check_dense(qkv, op, "qkv", kAnyGpu, at::kBFloat16, qkv.numel());
+    TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == 3 * heads * 128 && qkv.size(1) <= 1024 &&
+                    kfk::attention_d128_supported(static_cast<int>(qkv.size(1))),
+                op, ": qkv must be [B, S, 3*H*128] with S a multiple of 64 from 64 to 1024");
+    return {narrow(qkv.size(0), op, "B"), narrow(qkv.size(1), op, "S"), narrow(heads, op, "heads")};
+}
+
+// Fused self-attention at head dim 128: qkv [B, S, 3*H*128] bf16 contiguous -> (out [B, S, H*128] bf16, lse [B, H, S]
+// f32); causal: query q sees keys <= q.  No lengths at this head dim.
+std::vector<at::Tensor> attention_d128_forward(at::Tensor qkv, int64_t heads, double scale, int64_t seed, double p_drop,
+                                               bool causal) {
+    const auto [B, S, H] = check_qkv_d128(qkv, heads, "attention_d128_forward");
+    c10::DeviceGuard gd(qkv.device());
+    auto out = at::empty({B, S, H * 128}, qkv.options());
+    auto lse = at::empty({B, H, S}, qkv.options().dtype(at::kFloat));
+    kfk::launch_attention_d128_forward(bf16(qkv), bf16_mut(out), lse.data_ptr<float>(), B, S, H,
+                                       static_cast<float>(scale), static_cast<uint32_t>(seed),
+                                       static_cast<float>(p_drop), causal, stream_of(qkv, 0));
+    return {out, lse};
+}
+
+at::Tensor attention_d128_backward(at::Tensor qkv, at::Tensor out, at::Tensor lse, at::Tensor dout, int64_t heads,
+                                   double scale, int64_t seed, double p_drop, bool causal) {
+    const char *op = "attention_d128_backward";
+    const auto [B, S, H] = check_qkv_d128(qkv, heads, op);
+    const Dev dev = qkv.device();
+    check_dense(out, op, "out", dev, at::kBFloat16, out.numel());
+    TORCH_CHECK(out.sizes() == at::IntArrayRef({B, S, H * 128}),
+                "attention_d128_backward: out must be the forward's [B, S, H*128] output");
+    TORCH_CHECK(dout.sizes() == out.sizes() && dout.scalar_type() == at::kBFloat16 && dout.device() == qkv.device(),
+                "attention_d128_backward: dout must be bf16 of out's shape on qkv's device");
+    check_dense(lse, op, "lse", dev, at::kFloat, lse.numel());
+    TORCH_CHECK(lse.sizes() == at::IntArrayRef({B, H, S}),
+                "attention_d128_backward: lse must be the forward's [B, H, S] f32");
+    c10::DeviceGuard gd(qkv.device());
+    if (!dout.is_contiguous()) dout = dout.contiguous();
+    auto dqkv = at::empty_like(qkv);
+    auto dsum = at::empty({B, H, S}, lse.options());  // the dQ kernel fills it for the dK/dV kernel
+    kfk::launch_attention_d128_backward(bf16(qkv), bf16(out), lse.data_ptr<float>(), bf16(dout), bf16_mut(dqkv),
+                                        dsum.data_ptr<float>(), B, S, H, static_cast<float>(scale),
+                                        static_cast<uint32_t>(seed), static_cast<float>(p_drop), causal,
+                                        stream_of(qkv, 0));
+    return dqkv;
+}
+
 // y, s, mean, rstd = layernorm(x [+ r]) over the last dim (bf16 rows, f32 affine)
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> layernorm_forward(at::Tensor x, OptTensor r, at::Tensor gamma,
                                                                              at::Tensor beta, double eps, double p,
@@ -355,6 +402,15 @@ void bind_bert(py::module_ &m) {
           py::arg("qkv"), py::arg("out"), py::arg("lse"), py::arg("dout"), py::arg("heads"), py::arg("scale"),
           py::arg("seed"), py::arg("p_drop"), py::arg("stream_kernel") = false, py::arg("lengths") = py::none(),
           py::arg("causal") = false, py::arg("plain_order") = false);
+    m.def("attention_d128_supported", &kfk::attention_d128_supported);
+    m.def("attention_d128_forward", &attention_d128_forward,
+          "fused self-attention forward at head dim 128 (S 64..1024 in steps of 64, dropout, causal or not) -> (out, lse)",
+          py::arg("qkv"), py::arg("heads"), py::arg("scale"), py::arg("seed"), py::arg("p_drop"),
+          py::arg("causal") = false);
+    m.def("attention_d128_backward", &attention_d128_backward,
+          "fused self-attention backward at head dim 128 -> dqkv (S and causal as the forward)", py::arg("qkv"),
+          py::arg("out"), py::arg("lse"), py::arg("dout"), py::arg("heads"), py::arg("scale"), py::arg("seed"),
+          py::arg("p_drop"), py::arg("causal") = false);
     m.def("gemm_nt", &gemm_nt, py::arg("a"), py::arg("b"), py::arg("bias") = py::none(), py::arg("out") = py::none(),
           py::arg("accumulate") = false, py::arg("bn") = -1,
           "bf16 a[M,K] . b[N,K]^T (+bias) (+out) on the pipelined 256 x bn MFMA GEMM (gemm.hip)");

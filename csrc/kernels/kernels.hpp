@@ -524,5 +524,14 @@ void launch_attention_backward(const uint16_t *qkv, const uint16_t *out, const f
                                uint16_t *dqkv, int B, int S, int H, float scale, uint32_t seed, float p_drop,
                                hipStream_t s, float *dsum = nullptr, bool stream_kernel = false,
                                const int *lengths = nullptr, bool causal = false, bool plain_order = false);
+// Head dim 128 (attention_d128.hip): the same interface with qkv [B, S, 3, H, 128], out [B, S, H*128], every S that
+// is a multiple of 64 from 64 to 1024, bidirectional or causal; no lengths.  Kernels of their own (256-byte LDS rows,
+// Q in registers, dynamic LDS): nothing of the 64-wide family above is launched.  dsum is always needed.
+bool attention_d128_supported(int S);
+void launch_attention_d128_forward(const uint16_t *qkv, uint16_t *out, float *lse, int B, int S, int H, float scale,
+                                   uint32_t seed, float p_drop, bool causal, hipStream_t s);
+void launch_attention_d128_backward(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *dout,
+                                    uint16_t *dqkv, float *dsum, int B, int S, int H, float scale, uint32_t seed,
+                                    float p_drop, bool causal, hipStream_t s);
 
 }  // namespace kfk

@@ -6,7 +6,9 @@ torch's scaled_dot_product_attention (also for S > 128 with KUNGFU_ATTN_LONG=0).
 ``lengths`` (int32 [B], the valid tokens of each sequence) and stay on the fused kernels from S = 128 up:
 padded rows of the attention output are zero and add nothing to any gradient.  A general ``mask`` still
 takes the scaled_dot_product_attention path; giving both is an error.  ``BertLayer(x, causal=True)`` is the
-decoder block of models/gpt.py: the causal fused kernels, with neither mask nor lengths."""
+decoder block of models/gpt.py: the causal fused kernels, with neither mask nor lengths.  The head dim is
+``d / heads``: 64 (BERT, GPT) and 128 (``BertLayer(1024, 8, 4096)``: csrc/kernels/attention_d128.hip, S up to 1024,
+no ``lengths``) have fused kernels, any other head dim runs scaled_dot_product_attention."""
 import math
 
 import torch

@@ -2,7 +2,9 @@
 FFN 3072, GELU, learned positions, a context of 512 tokens, vocab 40478, tied output embedding, ~116 M
 parameters.  Architecturally BERT's encoder layer with a causal mask: the layers are ``BertLayer``s called
 with ``causal=True``, whose attention runs the triangular fused HIP kernels of ops/attention.py (S a multiple
-of 64 up to 1024; anything else ``F.scaled_dot_product_attention(is_causal=True)``)."""
+of 64 up to 1024; anything else ``F.scaled_dot_product_attention(is_causal=True)``).  The head dim is ``d / heads``:
+64 and 128 have fused kernels.  ``gpt_d128`` is the same model with GPT-3 / LLaMA-style heads of 128: d = 1024, 8 heads,
+FFN 4096, whose attention runs csrc/kernels/attention_d128.hip."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -47,6 +49,12 @@ class GPTLM(nn.Module):
 def gpt_base(**kw):
     kw.pop("fused_bn", None)
     return GPTLM(**kw)
+
+
+def gpt_d128(**kw):
+    """GPTLM with 8 heads of 128 (d = 1024, FFN 4096); the remaining defaults are GPTLM's."""
+    kw.pop("fused_bn", None)
+    return GPTLM(**{"d": 1024, "heads": 8, "ffn": 4096, **kw})
 
 
 def synthetic_lm_batch(batch: int, seq_len: int = 512, vocab: int = 40478, device=None, generator=None):

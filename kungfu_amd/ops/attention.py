@@ -32,6 +32,15 @@ is masked, so about half of the bidirectional call's work is never issued (profi
 layouts, same dropout hash, bitwise reproducible.  ``causal`` with ``lengths`` is a ``ValueError``: right padding
 cannot influence a valid causal row, so masking the loss is enough.  The fallback (CPU, f32, any other S, and
 S > 128 with ``KUNGFU_ATTN_LONG=0``) is ``F.scaled_dot_product_attention(..., is_causal=True)``.
+
+Head dim 128 (GPT-3 from 6.7 B up, the LLaMA family): the head dim is ``qkv.shape[2] // (3 * heads)``, and at 128
+``[B, S, 3*H*128]`` runs the kernels of csrc/kernels/attention_d128.hip, bidirectional or ``causal``, for every S that
+is a multiple of 64 from 64 to 1024: 256-byte LDS rows, the wave's Q rows in registers, 8 accumulator tiles, scale
+1 / sqrt(128), the same layouts, dropout hash and bitwise reproducibility (profiles/attention_d128.md).  There is no
+``lengths`` support at this head dim: head dim 128 with ``lengths`` runs :func:`_lengths_fallback`, and any other S, a
+CPU or f32 tensor, S > 128 with ``KUNGFU_ATTN_LONG=0`` and the (mask, S) pairs of ``_D128_ROUTED_AWAY`` run
+``F.scaled_dot_product_attention``.  Other head dims always do.  The module switch ``_D128_ENABLED = False`` sends
+every head dim 128 call to its fallback (for tests and measurements in one process).
 """
 from __future__ import annotations
 
@@ -73,6 +82,42 @@ class _AttnFn(torch.autograd.Function):
         return dqkv, None, None, None, None, None
 
 
+class _AttnD128Fn(torch.autograd.Function):
+    """Head dim 128: the kernels of attention_d128.hip."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads, p, seed, causal):
+        scale = 1.0 / math.sqrt(128.0)
+        out, lse = hip().attention_d128_forward(qkv, heads, scale, seed, p, causal)
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.heads, ctx.p, ctx.seed, ctx.scale, ctx.causal = heads, p, seed, scale, causal
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse = ctx.saved_tensors
+        dqkv = hip().attention_d128_backward(qkv, out, lse, dout.contiguous(), ctx.heads, ctx.scale, ctx.seed, ctx.p,
+                                             ctx.causal)
+        return dqkv, None, None, None, None
+
+
+# (causal, S) pairs at head dim 128 whose forward + backward did not beat the SDPA path by more than the measured
+# spread (profiles/attention_d128.md): they keep the fallback
+_D128_ROUTED_AWAY: frozenset = frozenset()
+# False: every head dim 128 call keeps its fallback, whatever S (KUNGFU_ATTN_LONG=0 leaves S <= 128 fused); tests and
+# tools/bench_attention.py set it to compare the two paths in one process
+_D128_ENABLED = True
+
+
+def eligible_d128(qkv: torch.Tensor, heads: int, lengths=None, causal: bool = False) -> bool:
+    """Whether the head dim 128 kernels serve this call: bf16, contiguous, on the GPU, S a multiple of 64 up to 1024
+    that the measurements did not route away, no ``lengths``; ``KUNGFU_ATTN_LONG=0`` keeps S > 128 off them."""
+    return (_D128_ENABLED and lengths is None and qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.dim() == 3
+            and qkv.is_contiguous() and qkv.shape[2] == 3 * heads * 128 and qkv.shape[1] <= 1024
+            and (_LONG_ENABLED or qkv.shape[1] <= 128) and (bool(causal), int(qkv.shape[1])) not in _D128_ROUTED_AWAY
+            and hip_available() and hip().attention_d128_supported(int(qkv.shape[1])))
+
+
 def eligible(qkv: torch.Tensor, heads: int, lengths=None, causal: bool = False) -> bool:
     """Whether the fused kernels serve this call; with ``lengths`` only the streaming family does
     (S >= 128, and not with ``KUNGFU_ATTN_LONG=0``); ``causal``: S a multiple of 64 up to 1024, no lengths."""
@@ -112,7 +157,7 @@ def _lengths_fallback(qkv: torch.Tensor, heads: int, p: float, lengths: torch.Te
 
 def self_attention(qkv: torch.Tensor, heads: int, p: float = 0.0, lengths: torch.Tensor | None = None,
                    causal: bool = False) -> torch.Tensor:
-    """softmax(Q K^T / sqrt(64)) V with dropout ``p`` on the probabilities, per head;
+    """softmax(Q K^T / sqrt(dh)) V with dropout ``p`` on the probabilities, per head (dh = 64 or 128 fused);
     ``qkv``: [B, S, 3*H*dh] -> [B, S, H*dh].  ``lengths`` (int32 [B], on qkv's device): the valid
     tokens of each padded sequence; ``causal``: query q attends to keys <= q (module docstring)."""
     B, S, D3 = qkv.shape
@@ -120,6 +165,10 @@ def self_attention(qkv: torch.Tensor, heads: int, p: float = 0.0, lengths: torch
         raise ValueError("self_attention: causal attention takes no lengths: right padding cannot reach a valid row")
     if lengths is not None:
         _check_lengths(qkv, lengths)
+    if D3 == 3 * heads * 128 and eligible_d128(qkv, heads, lengths, causal):
+        seed = int(torch.randint(0, 2**31 - 1, (1,)).item())  # CPU generator: no device sync
+        dropout_seed.base(qkv.device)
+        return _AttnD128Fn.apply(qkv, heads, float(p), seed, bool(causal))
     if eligible(qkv, heads, lengths, causal):
         seed = int(torch.randint(0, 2**31 - 1, (1,)).item())  # CPU generator: no device sync
         dropout_seed.base(qkv.device)  # registers the device seed word (graph replays advance it)

@@ -17,7 +17,12 @@ alternating the same way: the causal call in its heaviest-first workgroup order 
 bidirectional call at the same shape twice (S <= 512) and the SDPA ``is_causal=True`` path with BertLayer's permutes
 and copies.
 
-    python tools/bench_attention.py [calls] [--batch 128] [--seq 128] [--heads 12] [--lengths 0.5|random] [--causal]"""
+With ``--head-dim 128`` it times the head dim 128 kernels (attention_d128.hip), forward and backward separately,
+bidirectional or (``--causal``) causal, twice per round, against the SDPA path at the same head dim with the permutes,
+copy and concatenation.
+
+    python tools/bench_attention.py [calls] [--batch 128] [--seq 128] [--heads 12] [--lengths 0.5|random] [--causal]
+                                    [--head-dim 64|128]"""
 import argparse
 import os
 import sys
@@ -156,6 +161,40 @@ def causal(args, H, qkv, dout, scale):
             print(line, flush=True)
 
 
+def d128(args, H, qkv, dout):
+    """Head dim 128: forward and backward time of the attention_d128.hip kernels (timed twice per round: ``d128
+    again`` / ``d128`` is the run-to-run spread) and of the SDPA path with the permutes, the transposed output copy
+    and the dq/dk/dv concatenation, the variants alternating over the rounds; bidirectional, or causal with --causal."""
+    B, S, NH, c = args.batch, args.seq, args.heads, args.causal
+    scale = 128 ** -0.5
+    for p in (0.1, 0.0):
+        out, lse = H.attention_d128_forward(qkv, NH, scale, 1234, p, c)
+        q = qkv.clone().requires_grad_(True)
+
+        def sdpa_fwd():
+            qq, k, v = q.view(B, S, 3, NH, 128).permute(2, 0, 3, 1, 4)
+            a = torch.nn.functional.scaled_dot_product_attention(qq, k, v, dropout_p=p, is_causal=c)
+            return a.transpose(1, 2).reshape(B, S, NH * 128)
+
+        y = sdpa_fwd()
+        fused = (lambda: H.attention_d128_forward(qkv, NH, scale, 1234, p, c),
+                 lambda: H.attention_d128_backward(qkv, out, lse, dout, NH, scale, 1234, p, c))
+        variants = {"d128": fused, "d128 again": fused,
+                    "sdpa": (sdpa_fwd, lambda: torch.autograd.grad(y, q, dout, retain_graph=True))}
+        ts = {k: [] for k in variants}
+        for _ in range(args.rounds):
+            for k, (f, b) in variants.items():
+                ts[k].append((med(f, args.calls), med(b, args.calls)))
+        m = {}
+        for k, v in ts.items():
+            fs, bs, tot = sorted(f for f, _ in v), sorted(b for _, b in v), sorted(f + b for f, b in v)
+            m[k] = tot[len(tot) // 2]
+            print("causal=%d S=%d p=%.1f  %-10s fwd %7.1f us  bwd %7.1f us  fwd+bwd %7.1f us (min %7.1f max %7.1f) over %d rounds" % (
+                c, S, p, k, fs[len(fs) // 2], bs[len(bs) // 2], m[k], tot[0], tot[-1], len(v)), flush=True)
+        print("causal=%d S=%d p=%.1f  fwd+bwd: d128 / sdpa %.3f   d128 again / d128 %.3f" % (
+            c, S, p, m["d128"] / m["sdpa"], m["d128 again"] / m["d128"]), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("calls", nargs="?", type=int, default=20, help="calls to time")
@@ -166,16 +205,20 @@ def main():
     ap.add_argument("--causal", action="store_true", help="causal attention: the triangular kernels and what they replace")
     ap.add_argument("--rounds", type=int, default=5, help="--lengths / --causal: rounds the variants alternate over")
     ap.add_argument("--seed", type=int, default=0, help="--lengths random: seed of the lengths")
+    ap.add_argument("--head-dim", type=int, choices=(64, 128), default=64,
+                    help="128: the attention_d128.hip kernels against SDPA (with --causal: the causal ones)")
     args = ap.parse_args()
     n = args.calls
     H = hip()
     B, S, NH = args.batch, args.seq, args.heads
-    D = NH * 64
+    D = NH * args.head_dim
     torch.manual_seed(0)
     qkv = (torch.randn(B, S, 3 * D, device="cuda") * 0.5).bfloat16()
     dout = (torch.randn(B, S, D, device="cuda") * 0.1).bfloat16()
     scale = 64 ** -0.5
     print("B=%d S=%d H=%d" % (B, S, NH), flush=True)
+    if args.head_dim == 128:
+        return d128(args, H, qkv, dout)
     if args.causal:
         return causal(args, H, qkv, dout, scale)
     if args.lengths is not None:
