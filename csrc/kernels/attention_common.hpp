@@ -1,6 +1,6 @@
 // Device helpers shared by the fused attention kernels (attention.hip: whole sequence in LDS,
-// attention_long.hip, attention_lengths.hip and attention_causal.hip: streamed blocks; attention_d128.hip: head dim
-// 128, which adds its own 256-byte-row stager and block steps): the swizzled LDS image addressing, the MFMA operand
+// attention_long.hip, attention_lengths.hip and attention_causal.hip: streamed blocks; attention_d128.hip and
+// attention_gqa.hip: head dim 128, whose 256-byte-row stager and block steps are attention_d128.hpp's): the swizzled LDS image addressing, the MFMA operand
 // fragments, the dropout hash, the LDS-DMA staging and the kernel argument block.  Private to
 // those files: everything sits in an unnamed namespace.
 #pragma once

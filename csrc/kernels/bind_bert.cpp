@@ -224,6 +224,59 @@ at::Tensor attention_d128_backward(at::Tensor qkv, at::Tensor out, at::Tensor ls
     return dqkv;
 }
 
+// Grouped-query heads at head dim 128 (attention_gqa.hip): contiguous bf16 [B, S, (H + 2*Hkv)*128] with H % Hkv == 0
+// and S a multiple of 64 up to 1024: {B, S, H, Hkv}
+std::tuple<int, int, int, int> check_qkv_gqa(const at::Tensor &qkv, int64_t heads, int64_t kv_heads, const char *op) {
+    TORCH_CHECK(kv_heads >= 1 && heads >= kv_heads && heads % kv_heads == 0, op,
+                ": kv_heads must be at least 1 and divide heads, got heads ", heads, ", kv_heads ", kv_heads);
+    check_dense(qkv, op, "qkv", kAnyGpu, at::kBFloat16, qkv.numel());
+    const int H = narrow(heads, op, "heads"), Hkv = narrow(kv_heads, op, "kv_heads");
+    TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == (heads + 2 * kv_heads) * 128 && qkv.size(1) <= 1024 &&
+                    kfk::attention_gqa_supported(static_cast<int>(qkv.size(1)), H, Hkv),
+                op, ": qkv must be [B, S, (H + 2*Hkv)*128] with S a multiple of 64 from 64 to 1024");
+    check_extent32(op, "the workgroup count", {qkv.size(0), heads, qkv.size(1) / 64});
+    return {narrow(qkv.size(0), op, "B"), narrow(qkv.size(1), op, "S"), H, Hkv};
+}
+
+// Fused grouped-query self-attention at head dim 128: qkv [B, S, (H + 2*Hkv)*128] bf16 contiguous (query heads, key
+// heads, value heads; query head h reads K/V head h / (H / Hkv)) -> (out [B, S, H*128] bf16, lse [B, H, S] f32)
+std::vector<at::Tensor> attention_gqa_forward(at::Tensor qkv, int64_t heads, int64_t kv_heads, double scale,
+                                              int64_t seed, double p_drop, bool causal) {
+    const auto [B, S, H, Hkv] = check_qkv_gqa(qkv, heads, kv_heads, "attention_gqa_forward");
+    c10::DeviceGuard gd(qkv.device());
+    auto out = at::empty({B, S, H * 128}, qkv.options());
+    auto lse = at::empty({B, H, S}, qkv.options().dtype(at::kFloat));
+    kfk::launch_attention_gqa_forward(bf16(qkv), bf16_mut(out), lse.data_ptr<float>(), B, S, H, Hkv,
+                                      static_cast<float>(scale), static_cast<uint32_t>(seed),
+                                      static_cast<float>(p_drop), causal, stream_of(qkv, 0));
+    return {out, lse};
+}
+
+// -> dqkv in qkv's layout; dk / dv of a K/V head are the f32 sums over its group's query heads, rounded once
+at::Tensor attention_gqa_backward(at::Tensor qkv, at::Tensor out, at::Tensor lse, at::Tensor dout, int64_t heads,
+                                  int64_t kv_heads, double scale, int64_t seed, double p_drop, bool causal) {
+    const char *op = "attention_gqa_backward";
+    const auto [B, S, H, Hkv] = check_qkv_gqa(qkv, heads, kv_heads, op);
+    const Dev dev = qkv.device();
+    check_dense(out, op, "out", dev, at::kBFloat16, out.numel());
+    TORCH_CHECK(out.sizes() == at::IntArrayRef({B, S, H * 128}),
+                "attention_gqa_backward: out must be the forward's [B, S, H*128] output");
+    TORCH_CHECK(dout.sizes() == out.sizes() && dout.scalar_type() == at::kBFloat16 && dout.device() == qkv.device(),
+                "attention_gqa_backward: dout must be bf16 of out's shape on qkv's device");
+    check_dense(lse, op, "lse", dev, at::kFloat, lse.numel());
+    TORCH_CHECK(lse.sizes() == at::IntArrayRef({B, H, S}),
+                "attention_gqa_backward: lse must be the forward's [B, H, S] f32");
+    c10::DeviceGuard gd(qkv.device());
+    if (!dout.is_contiguous()) dout = dout.contiguous();
+    auto dqkv = at::empty_like(qkv);
+    auto dsum = at::empty({B, H, S}, lse.options());  // the dQ kernel fills it for the dK/dV kernel
+    kfk::launch_attention_gqa_backward(bf16(qkv), bf16(out), lse.data_ptr<float>(), bf16(dout), bf16_mut(dqkv),
+                                       dsum.data_ptr<float>(), B, S, H, Hkv, static_cast<float>(scale),
+                                       static_cast<uint32_t>(seed), static_cast<float>(p_drop), causal,
+                                       stream_of(qkv, 0));
+    return dqkv;
+}
+
 // y, s, mean, rstd = layernorm(x [+ r]) over the last dim (bf16 rows, f32 affine)
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> layernorm_forward(at::Tensor x, OptTensor r, at::Tensor gamma,
                                                                              at::Tensor beta, double eps, double p,
@@ -411,6 +464,18 @@ void bind_bert(py::module_ &m) {
           "fused self-attention backward at head dim 128 -> dqkv (S and causal as the forward)", py::arg("qkv"),
           py::arg("out"), py::arg("lse"), py::arg("dout"), py::arg("heads"), py::arg("scale"), py::arg("seed"),
           py::arg("p_drop"), py::arg("causal") = false);
+    m.def("attention_gqa_supported", &kfk::attention_gqa_supported, py::arg("S"), py::arg("heads"),
+          py::arg("kv_heads"));
+    m.def("attention_gqa_forward", &attention_gqa_forward,
+          "fused grouped-query self-attention forward at head dim 128: qkv [B, S, (heads + 2*kv_heads)*128] (query, "
+          "key, value heads; query head h reads K/V head h / (heads / kv_heads)), S 64..1024 in steps of 64, dropout, "
+          "causal or not -> (out [B, S, heads*128], lse [B, heads, S])",
+          py::arg("qkv"), py::arg("heads"), py::arg("kv_heads"), py::arg("scale"), py::arg("seed"), py::arg("p_drop"),
+          py::arg("causal") = false);
+    m.def("attention_gqa_backward", &attention_gqa_backward,
+          "fused grouped-query self-attention backward -> dqkv in qkv's layout (dk / dv summed over each group in f32)",
+          py::arg("qkv"), py::arg("out"), py::arg("lse"), py::arg("dout"), py::arg("heads"), py::arg("kv_heads"),
+          py::arg("scale"), py::arg("seed"), py::arg("p_drop"), py::arg("causal") = false);
     m.def("gemm_nt", &gemm_nt, py::arg("a"), py::arg("b"), py::arg("bias") = py::none(), py::arg("out") = py::none(),
           py::arg("accumulate") = false, py::arg("bn") = -1,
           "bf16 a[M,K] . b[N,K]^T (+bias) (+out) on the pipelined 256 x bn MFMA GEMM (gemm.hip)");

@@ -533,5 +533,16 @@ void launch_attention_d128_forward(const uint16_t *qkv, uint16_t *out, float *ls
 void launch_attention_d128_backward(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *dout,
                                     uint16_t *dqkv, float *dsum, int B, int S, int H, float scale, uint32_t seed,
                                     float p_drop, bool causal, hipStream_t s);
+// Grouped-query attention at head dim 128 (attention_gqa.hip): H query heads share Hkv = H / G key/value heads, query
+// head h reads K/V head h / G.  qkv and dqkv [B, S, (H + 2 Hkv) * 128] (the H query heads, the Hkv key heads, the Hkv
+// value heads of a row), out [B, S, H*128], lse and dsum [B, H, S]; S as above, bidirectional or causal, no lengths.
+// dK/dV are summed over a group's query heads in registers (one workgroup per K/V head and key block) and rounded once.
+// Hkv == H is attention_d128's layout and its results bit for bit.
+bool attention_gqa_supported(int S, int heads, int kv_heads);
+void launch_attention_gqa_forward(const uint16_t *qkv, uint16_t *out, float *lse, int B, int S, int H, int Hkv,
+                                  float scale, uint32_t seed, float p_drop, bool causal, hipStream_t s);
+void launch_attention_gqa_backward(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *dout,
+                                   uint16_t *dqkv, float *dsum, int B, int S, int H, int Hkv, float scale,
+                                   uint32_t seed, float p_drop, bool causal, hipStream_t s);
 
 }  // namespace kfk

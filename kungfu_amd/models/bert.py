@@ -8,7 +8,9 @@ padded rows of the attention output are zero and add nothing to any gradient.  A
 takes the scaled_dot_product_attention path; giving both is an error.  ``BertLayer(x, causal=True)`` is the
 decoder block of models/gpt.py: the causal fused kernels, with neither mask nor lengths.  The head dim is
 ``d / heads``: 64 (BERT, GPT) and 128 (``BertLayer(1024, 8, 4096)``: csrc/kernels/attention_d128.hip, S up to 1024,
-no ``lengths``) have fused kernels, any other head dim runs scaled_dot_product_attention."""
+no ``lengths``) have fused kernels, any other head dim runs scaled_dot_product_attention.
+``BertLayer(..., kv_heads=Hkv)`` is grouped-query attention: one projection of ``heads + 2*Hkv`` heads, at head dim 128 on
+csrc/kernels/attention_gqa.hip (neither mask nor lengths)."""
 import math
 
 import torch
@@ -23,12 +25,15 @@ from ..ops.linear import gelu, residual_link
 
 
 class BertLayer(nn.Module):
-    def __init__(self, d=768, heads=12, ffn=3072, dropout=0.1):
+    def __init__(self, d=768, heads=12, ffn=3072, dropout=0.1, kv_heads=None):
         super().__init__()
         from ..ops.layernorm import AddLayerNorm
 
         self.heads = heads
-        self.qkv = nn.Linear(d, 3 * d)
+        # grouped-query heads: kv_heads K/V heads shared by heads / kv_heads query heads each, one projection of
+        # (heads + 2 kv_heads) heads (ops/attention.py); None: as many K/V heads as query heads
+        self.kv_heads = kv_heads
+        self.qkv = nn.Linear(d, 3 * d if kv_heads is None else (heads + 2 * kv_heads) * (d // heads))
         self.out = nn.Linear(d, d)
         # fused residual-add + LayerNorm (HIP, bf16 residual stream) -- torch.nn.LayerNorm
         # parameters and state_dict keys, torch composition off the GPU fast path
@@ -49,7 +54,11 @@ class BertLayer(nn.Module):
         # its gradient of x to the projection's data-gradient GEMM (ops.linear.ResidualLink)
         residual_link(x)
         qkv = self.qkv(x)
-        if causal:  # the triangular kernels of attention_causal.hip (GPT, models/gpt.py)
+        if self.kv_heads is not None:
+            if mask is not None or lengths is not None:
+                raise ValueError("BertLayer: kv_heads takes neither mask nor lengths")
+            a = self_attention(qkv, self.heads, p, causal=causal, kv_heads=self.kv_heads)
+        elif causal:  # the triangular kernels of attention_causal.hip (GPT, models/gpt.py)
             a = self_attention(qkv, self.heads, p, causal=True)
         elif mask is None:
             # fused HIP attention straight from / into the projections' layouts (SDPA off that path)

@@ -4,7 +4,8 @@ parameters.  Architecturally BERT's encoder layer with a causal mask: the layers
 with ``causal=True``, whose attention runs the triangular fused HIP kernels of ops/attention.py (S a multiple
 of 64 up to 1024; anything else ``F.scaled_dot_product_attention(is_causal=True)``).  The head dim is ``d / heads``:
 64 and 128 have fused kernels.  ``gpt_d128`` is the same model with GPT-3 / LLaMA-style heads of 128: d = 1024, 8 heads,
-FFN 4096, whose attention runs csrc/kernels/attention_d128.hip."""
+FFN 4096, whose attention runs csrc/kernels/attention_d128.hip; ``gpt_gqa`` is ``gpt_d128`` with LLaMA-2-style
+grouped-query attention (``kv_heads=2``: csrc/kernels/attention_gqa.hip)."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -16,11 +17,11 @@ from .bert import BertLayer
 
 
 class GPTLM(nn.Module):
-    def __init__(self, vocab=40478, d=768, layers=12, heads=12, ffn=3072, max_pos=512, dropout=0.1):
+    def __init__(self, vocab=40478, d=768, layers=12, heads=12, ffn=3072, max_pos=512, dropout=0.1, kv_heads=None):
         super().__init__()
         self.tok = nn.Embedding(vocab, d)
         self.pos = nn.Embedding(max_pos, d)
-        self.layers = nn.ModuleList([BertLayer(d, heads, ffn, dropout) for _ in range(layers)])
+        self.layers = nn.ModuleList([BertLayer(d, heads, ffn, dropout, kv_heads) for _ in range(layers)])
         self.dropout = dropout
         self.apply(self._init)
 
@@ -55,6 +56,11 @@ def gpt_d128(**kw):
     """GPTLM with 8 heads of 128 (d = 1024, FFN 4096); the remaining defaults are GPTLM's."""
     kw.pop("fused_bn", None)
     return GPTLM(**{"d": 1024, "heads": 8, "ffn": 4096, **kw})
+
+
+def gpt_gqa(**kw):
+    """``gpt_d128`` with grouped-query attention: its 8 query heads of 128 share 2 K/V heads (groups of 4)."""
+    return gpt_d128(**{"kv_heads": 2, **kw})
 
 
 def synthetic_lm_batch(batch: int, seq_len: int = 512, vocab: int = 40478, device=None, generator=None):

@@ -41,6 +41,19 @@ is a multiple of 64 from 64 to 1024: 256-byte LDS rows, the wave's Q rows in reg
 CPU or f32 tensor, S > 128 with ``KUNGFU_ATTN_LONG=0`` and the (mask, S) pairs of ``_D128_ROUTED_AWAY`` run
 ``F.scaled_dot_product_attention``.  Other head dims always do.  The module switch ``_D128_ENABLED = False`` sends
 every head dim 128 call to its fallback (for tests and measurements in one process).
+
+Grouped-query attention (LLaMA-2 70B and later; one K/V head: multi-query attention):
+``self_attention(qkv, heads, p, causal=..., kv_heads=Hkv)`` with ``heads % Hkv == 0`` takes ``[B, S, (H + 2*Hkv)*dh]``,
+the output of one ``nn.Linear(d, (H + 2*Hkv)*dh)``: the H query heads, then the Hkv key heads, then the Hkv value
+heads.  Query head ``h`` reads K/V head ``h // (H // Hkv)``; the result is ``[B, S, H*dh]`` and the gradient one tensor in
+the input's layout.  ``kv_heads=None`` or ``kv_heads == heads`` is the call without the keyword, through the paths
+above.  At head dim 128 the kernels of csrc/kernels/attention_gqa.hip serve the domain of the head dim 128 kernels
+(bf16, contiguous, S a multiple of 64 from 64 to 1024, either mask): K and V are never expanded, the G workgroups that
+share a K/V head are dispatched next to each other, and the dK/dV kernel sums a group's query heads in its f32
+registers and rounds once (profiles/attention_gqa.md).  The dropout hash stays keyed on the query head.  ``kv_heads``
+with ``lengths`` is a ``ValueError``.  Everything else (CPU, f32, other S, head dim 64, S > 128 with
+``KUNGFU_ATTN_LONG=0``, the (mask, S, G) triples of ``_GQA_ROUTED_AWAY``, ``_GQA_ENABLED = False``) expands K/V over the
+group and runs ``F.scaled_dot_product_attention``; autograd sums the group's dk / dv.
 """
 from __future__ import annotations
 
@@ -118,6 +131,61 @@ def eligible_d128(qkv: torch.Tensor, heads: int, lengths=None, causal: bool = Fa
             and hip_available() and hip().attention_d128_supported(int(qkv.shape[1])))
 
 
+class _AttnGQAFn(torch.autograd.Function):
+    """Grouped-query heads at head dim 128: the kernels of attention_gqa.hip."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads, kv_heads, p, seed, causal):
+        scale = 1.0 / math.sqrt(128.0)
+        out, lse = hip().attention_gqa_forward(qkv, heads, kv_heads, scale, seed, p, causal)
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.heads, ctx.kv_heads, ctx.p, ctx.seed, ctx.scale, ctx.causal = heads, kv_heads, p, seed, scale, causal
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse = ctx.saved_tensors
+        dqkv = hip().attention_gqa_backward(qkv, out, lse, dout.contiguous(), ctx.heads, ctx.kv_heads, ctx.scale,
+                                            ctx.seed, ctx.p, ctx.causal)
+        return dqkv, None, None, None, None, None
+
+
+# (causal, S, G) triples whose forward + backward did not beat the better of the two alternatives (K/V expanded for the
+# head dim 128 kernels plus the group sum; the SDPA fallback) by more than the measured spread
+# (profiles/attention_gqa.md): they keep the fallback
+_GQA_ROUTED_AWAY: frozenset = frozenset()
+# False: every kv_heads call keeps its fallback (tests and tools/bench_attention.py compare the paths in one process)
+_GQA_ENABLED = True
+
+
+def eligible_gqa(qkv: torch.Tensor, heads: int, kv_heads: int, causal: bool = False) -> bool:
+    """Whether the grouped-query kernels serve this call: head dim 128, bf16, contiguous, on the GPU, S a multiple of
+    64 up to 1024 that the measurements did not route away; ``KUNGFU_ATTN_LONG=0`` keeps S > 128 off them."""
+    return (_GQA_ENABLED and qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.dim() == 3 and qkv.is_contiguous()
+            and qkv.shape[2] == (heads + 2 * kv_heads) * 128 and qkv.shape[1] <= 1024
+            and (_LONG_ENABLED or qkv.shape[1] <= 128)
+            and (bool(causal), int(qkv.shape[1]), heads // kv_heads) not in _GQA_ROUTED_AWAY
+            and hip_available() and hip().attention_gqa_supported(int(qkv.shape[1]), heads, kv_heads))
+
+
+def _gqa_attention(qkv: torch.Tensor, heads: int, kv_heads: int, p: float, causal: bool) -> torch.Tensor:
+    """``self_attention`` with ``kv_heads < heads``: the fused kernels, else K/V expanded over the group for SDPA."""
+    B, S, W = qkv.shape
+    if W % (heads + 2 * kv_heads):
+        raise ValueError("self_attention: qkv's last dim %d is not (heads + 2*kv_heads) * dh for heads %d, kv_heads %d"
+                         % (W, heads, kv_heads))
+    if eligible_gqa(qkv, heads, kv_heads, causal):
+        seed = int(torch.randint(0, 2**31 - 1, (1,)).item())  # CPU generator: no device sync
+        dropout_seed.base(qkv.device)
+        return _AttnGQAFn.apply(qkv, heads, kv_heads, float(p), seed, bool(causal))
+    dh, G = W // (heads + 2 * kv_heads), heads // kv_heads
+    q, k, v = qkv.split((heads * dh, kv_heads * dh, kv_heads * dh), dim=2)
+    q = q.view(B, S, heads, dh).transpose(1, 2)
+    k, v = (t.view(B, S, kv_heads, dh).transpose(1, 2).repeat_interleave(G, dim=1) for t in (k, v))
+    a = F.scaled_dot_product_attention(q, k, v, dropout_p=p, is_causal=causal)
+    return a.transpose(1, 2).reshape(B, S, heads * dh)
+
+
 def eligible(qkv: torch.Tensor, heads: int, lengths=None, causal: bool = False) -> bool:
     """Whether the fused kernels serve this call; with ``lengths`` only the streaming family does
     (S >= 128, and not with ``KUNGFU_ATTN_LONG=0``); ``causal``: S a multiple of 64 up to 1024, no lengths."""
@@ -156,13 +224,22 @@ def _lengths_fallback(qkv: torch.Tensor, heads: int, p: float, lengths: torch.Te
 
 
 def self_attention(qkv: torch.Tensor, heads: int, p: float = 0.0, lengths: torch.Tensor | None = None,
-                   causal: bool = False) -> torch.Tensor:
+                   causal: bool = False, kv_heads: int | None = None) -> torch.Tensor:
     """softmax(Q K^T / sqrt(dh)) V with dropout ``p`` on the probabilities, per head (dh = 64 or 128 fused);
     ``qkv``: [B, S, 3*H*dh] -> [B, S, H*dh].  ``lengths`` (int32 [B], on qkv's device): the valid
-    tokens of each padded sequence; ``causal``: query q attends to keys <= q (module docstring)."""
+    tokens of each padded sequence; ``causal``: query q attends to keys <= q; ``kv_heads``: grouped-query heads,
+    ``qkv`` [B, S, (H + 2*kv_heads)*dh] (module docstring)."""
     B, S, D3 = qkv.shape
     if causal and lengths is not None:
         raise ValueError("self_attention: causal attention takes no lengths: right padding cannot reach a valid row")
+    if kv_heads is not None:
+        if kv_heads < 1 or heads % kv_heads:
+            raise ValueError("self_attention: kv_heads must be at least 1 and divide heads, got heads %d, kv_heads %d"
+                             % (heads, kv_heads))
+        if lengths is not None:
+            raise ValueError("self_attention: grouped-query attention (kv_heads) takes no lengths")
+        if kv_heads != heads:  # (kv_heads == heads is the call without the keyword: the code below)
+            return _gqa_attention(qkv, heads, kv_heads, p, causal)
     if lengths is not None:
         _check_lengths(qkv, lengths)
     if D3 == 3 * heads * 128 and eligible_d128(qkv, heads, lengths, causal):

@@ -21,8 +21,12 @@ With ``--head-dim 128`` it times the head dim 128 kernels (attention_d128.hip), 
 bidirectional or (``--causal``) causal, twice per round, against the SDPA path at the same head dim with the permutes,
 copy and concatenation.
 
+With ``--head-dim 128 --kv-heads N`` it times the grouped-query kernels (attention_gqa.hip) against the two ways to
+serve the call without them: K/V expanded for the head dim 128 kernels plus the group sum of dk / dv, and the SDPA
+fallback.
+
     python tools/bench_attention.py [calls] [--batch 128] [--seq 128] [--heads 12] [--lengths 0.5|random] [--causal]
-                                    [--head-dim 64|128]"""
+                                    [--head-dim 64|128] [--kv-heads N]"""
 import argparse
 import os
 import sys
@@ -195,6 +199,68 @@ def d128(args, H, qkv, dout):
             c, S, p, m["d128"] / m["sdpa"], m["d128 again"] / m["d128"]), flush=True)
 
 
+def gqa(args, H):
+    """Grouped-query heads at head dim 128 (``--kv-heads``): forward and backward time of the attention_gqa.hip
+    kernels (twice per round: ``gqa again`` / ``gqa`` is the run-to-run spread) against what serves the same call
+    without them: ``expand`` (repeat_interleave of K/V into [B, S, 3*H*128], the attention_d128.hip kernels on it, the
+    torch group sum of the bf16 dk / dv slices and the concatenation into the grouped layout) and ``sdpa``
+    (self_attention's fallback with ``_GQA_ENABLED = False``).  The variants alternate over the rounds."""
+    B, S, NH, NKV, c = args.batch, args.seq, args.heads, args.kv_heads, args.causal
+    G, scale = NH // NKV, 128 ** -0.5
+    torch.manual_seed(0)
+    qkv = (torch.randn(B, S, (NH + 2 * NKV) * 128, device="cuda") * 0.5).bfloat16()
+    dout = (torch.randn(B, S, NH * 128, device="cuda") * 0.1).bfloat16()
+
+    def expand():
+        q, k, v = qkv.split((NH * 128, NKV * 128, NKV * 128), dim=2)
+        k, v = (t.view(B, S, NKV, 128).repeat_interleave(G, dim=2).view(B, S, NH * 128) for t in (k, v))
+        return torch.cat((q, k, v), dim=2)
+
+    for p in (0.1, 0.0):
+        out, lse = H.attention_gqa_forward(qkv, NH, NKV, scale, 1234, p, c)
+        x = expand()
+        xout, xlse = H.attention_d128_forward(x, NH, scale, 1234, p, c)
+        assert torch.equal(out, xout)
+
+        def expand_bwd():
+            dx = H.attention_d128_backward(x, xout, xlse, dout, NH, scale, 1234, p, c).view(B, S, 3, NKV, G, 128)
+            return torch.cat((dx[:, :, 0].reshape(B, S, NH * 128), dx[:, :, 1].sum(3).view(B, S, NKV * 128),
+                              dx[:, :, 2].sum(3).view(B, S, NKV * 128)), dim=2)
+
+        q = qkv.clone().requires_grad_(True)
+        attn._GQA_ENABLED = False
+        try:
+            y = attn.self_attention(q, NH, p, causal=c, kv_heads=NKV)
+        finally:
+            attn._GQA_ENABLED = True
+        assert type(y.grad_fn).__name__ != "_AttnGQAFnBackward"
+
+        def sdpa_fwd():
+            attn._GQA_ENABLED = False
+            try:
+                return attn.self_attention(q, NH, p, causal=c, kv_heads=NKV)
+            finally:
+                attn._GQA_ENABLED = True
+
+        fused = (lambda: H.attention_gqa_forward(qkv, NH, NKV, scale, 1234, p, c),
+                 lambda: H.attention_gqa_backward(qkv, out, lse, dout, NH, NKV, scale, 1234, p, c))
+        variants = {"gqa": fused, "gqa again": fused,
+                    "expand": (lambda: H.attention_d128_forward(expand(), NH, scale, 1234, p, c), expand_bwd),
+                    "sdpa": (sdpa_fwd, lambda: torch.autograd.grad(y, q, dout, retain_graph=True))}
+        ts = {k: [] for k in variants}
+        for _ in range(args.rounds):
+            for k, (f, b) in variants.items():
+                ts[k].append((med(f, args.calls), med(b, args.calls)))
+        m = {}
+        for k, v in ts.items():
+            fs, bs, tot = sorted(f for f, _ in v), sorted(b for _, b in v), sorted(f + b for f, b in v)
+            m[k] = tot[len(tot) // 2]
+            print("causal=%d S=%d B=%d G=%d p=%.1f  %-10s fwd %7.1f us  bwd %7.1f us  fwd+bwd %7.1f us (min %7.1f max %7.1f) over %d rounds" % (
+                c, S, B, G, p, k, fs[len(fs) // 2], bs[len(bs) // 2], m[k], tot[0], tot[-1], len(v)), flush=True)
+        print("causal=%d S=%d B=%d G=%d p=%.1f  fwd+bwd: gqa / expand %.3f   gqa / sdpa %.3f   gqa again / gqa %.3f" % (
+            c, S, B, G, p, m["gqa"] / m["expand"], m["gqa"] / m["sdpa"], m["gqa again"] / m["gqa"]), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("calls", nargs="?", type=int, default=20, help="calls to time")
@@ -207,10 +273,18 @@ def main():
     ap.add_argument("--seed", type=int, default=0, help="--lengths random: seed of the lengths")
     ap.add_argument("--head-dim", type=int, choices=(64, 128), default=64,
                     help="128: the attention_d128.hip kernels against SDPA (with --causal: the causal ones)")
+    ap.add_argument("--kv-heads", type=int, default=None,
+                    help="grouped-query heads (needs --head-dim 128): the attention_gqa.hip kernels against the "
+                         "expanded-K/V attention_d128.hip path and SDPA")
     args = ap.parse_args()
     n = args.calls
     H = hip()
     B, S, NH = args.batch, args.seq, args.heads
+    if args.kv_heads is not None:
+        if args.head_dim != 128 or args.kv_heads < 1 or NH % args.kv_heads:
+            ap.error("--kv-heads needs --head-dim 128 and a divisor of --heads")
+        print("B=%d S=%d H=%d Hkv=%d" % (B, S, NH, args.kv_heads), flush=True)
+        return gqa(args, H)
     D = NH * args.head_dim
     torch.manual_seed(0)
     qkv = (torch.randn(B, S, 3 * D, device="cuda") * 0.5).bfloat16()
