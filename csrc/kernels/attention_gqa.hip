@@ -61,6 +61,16 @@
 //   dsum          the dQ kernel writes all 64 rows of its block and every (query head, block) has a workgroup: all
 //                 [B, H, S] values are written before the dK/dV kernel reads them (stream order).
 //
+// Rotary position embeddings (template parameter ROPE of the dQ and dK/dV kernels; attention_rope.hip rotates the
+// forward's input): qkv holds the rotated Q and K, so the sums above are the gradients of the rotated heads, and
+// the epilogue applies the transposed rotation before the store.  A lane's tiles o[c] and o[c + 4] (dk[c], dk[c + 4]),
+// c = 0 .. 3, hold columns i = 16 c + 4 lg + r and i + 64 of the same row, a rotary pair of the half-split convention:
+//   dx[i] = dx'[i] cos[t][i] + dx'[i + 64] sin[t][i]        dx[i + 64] = dx'[i + 64] cos[t][i] - dx'[i] sin[t][i]
+// in f32, no shuffle, no LDS, ahead of * scale and the one rounding to bf16.  t is the lane's query row (dQ) or key row
+// (dK): row < S of the f32 [S, 64] tables cos and sin, floats 16 c + 4 lg .. + 3 <= 63 as one 16-byte load each.  dv is
+// not touched.  The tables are two kernel arguments of their own (unused, and null, without ROPE); ROPE = false is the
+// code it was.
+//
 // Compiled without packed f32 instructions (KFK_NO_PK_F32), the precaution attention_lengths.hip's header explains.
 #include "attention_d128.hpp"
 
@@ -139,8 +149,24 @@ KFK_NO_PK_F32 __global__ __launch_bounds__(256, 2) void attn_gqa_fwd_kernel(Attn
     }
 }
 
-template <bool CAUSAL>
-KFK_NO_PK_F32 __global__ __launch_bounds__(256) void attn_gqa_dq_kernel(AttnArgs a, float *dsum_g, int Hkv, int S) {
+// The transposed rotation of a rotary pair of gradient tiles, in place (header: Rotary position embeddings): lo holds
+// columns 16 c + 4 lg + r, hi the columns 64 on, of table row t.
+__device__ __forceinline__ void rope_transposed(const float *cos_t, const float *sin_t, int t, int c, int lg, f32x4 &lo,
+                                                f32x4 &hi) {
+    const float4 cs = *reinterpret_cast<const float4 *>(cos_t + t * (D2 / 2) + 16 * c + 4 * lg);
+    const float4 sn = *reinterpret_cast<const float4 *>(sin_t + t * (D2 / 2) + 16 * c + 4 * lg);
+    const float cv[4] = {cs.x, cs.y, cs.z, cs.w}, sv[4] = {sn.x, sn.y, sn.z, sn.w};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float x = lo[r], y = hi[r];
+        lo[r] = fmaf(x, cv[r], y * sv[r]);
+        hi[r] = fmaf(y, cv[r], -(x * sv[r]));
+    }
+}
+
+template <bool CAUSAL, bool ROPE>
+KFK_NO_PK_F32 __global__ __launch_bounds__(256) void attn_gqa_dq_kernel(AttnArgs a, float *dsum_g, int Hkv, int S,
+                                                                        const float *cos_t, const float *sin_t) {
     extern __shared__ __attribute__((aligned(1024))) uint8_t lds[];
     uint8_t *ring = lds, *Si = lds + 4 * IMG;  // ring: 2 x (K, V)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -208,6 +234,10 @@ KFK_NO_PK_F32 __global__ __launch_bounds__(256) void attn_gqa_dq_kernel(AttnArgs
             for (int c = 0; c < TD; ++c) o[c] = mfma(ka[c], sb, o[c]);
         }
     }
+    if constexpr (ROPE) {  // the position is the query row
+#pragma unroll
+        for (int c = 0; c < TD / 2; ++c) rope_transposed(cos_t, sin_t, row, c, lg, o[c], o[c + TD / 2]);
+    }
 #pragma unroll
     for (int c = 0; c < TD; ++c) {
         uint16_t *dst = a.dqkv + (static_cast<int64_t>(b) * S + row) * RS + h * D2 + 16 * c + 4 * lg;
@@ -270,9 +300,10 @@ __device__ __forceinline__ void dkv_step(const AttnArgs &a, const float *dsum_g,
     }
 }
 
-template <bool CAUSAL>
+template <bool CAUSAL, bool ROPE>
 KFK_NO_PK_F32 __global__ __launch_bounds__(256) void attn_gqa_dkv_kernel(AttnArgs a, const float *dsum_g, int Hkv,
-                                                                         int S) {
+                                                                         int S, const float *cos_t,
+                                                                         const float *sin_t) {
     extern __shared__ __attribute__((aligned(1024))) uint8_t lds[];  // K, V resident; ring 2 x (Q, dO); P_drop; dS
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nbs = S / BK, G = a.H / Hkv;
@@ -310,6 +341,11 @@ KFK_NO_PK_F32 __global__ __launch_bounds__(256) void attn_gqa_dkv_kernel(AttnArg
         for (; qb < nbs; ++qb, slot ^= 1)
             dkv_step<false>(a, dsum_g, seed, g, b, h, qb, kbk, slot, lds, wave, lane, dv, dk);
     }
+    if constexpr (ROPE) {  // the position is the key row
+#pragma unroll
+        for (int c = 0; c < TD / 2; ++c)
+            rope_transposed(cos_t, sin_t, kbk * BK + w0 + lc, c, lg, dk[c], dk[c + TD / 2]);
+    }
     uint16_t *dkv0 = a.dqkv + (static_cast<int64_t>(b) * S + kbk * BK) * RS;
 #pragma unroll
     for (int c = 0; c < TD; ++c) {
@@ -334,14 +370,16 @@ void forward(const AttnArgs &a, int Hkv, int grid, int S, hipStream_t s) {
     attn_gqa_fwd_kernel<CAUSAL><<<grid, 256, FWD_LDS, s>>>(a, Hkv, S);
 }
 
-template <bool CAUSAL>
-void backward(const AttnArgs &a, float *dsum, int Hkv, int B, int S, hipStream_t s) {
-    static const bool attr = (raise_lds(attn_gqa_dq_kernel<CAUSAL>, DQ_LDS),
-                              raise_lds(attn_gqa_dkv_kernel<CAUSAL>, DKV_LDS), true);
+template <bool CAUSAL, bool ROPE>
+void backward(const AttnArgs &a, float *dsum, int Hkv, int B, int S, const float *cos, const float *sin,
+              hipStream_t s) {
+    static const bool attr = (raise_lds(attn_gqa_dq_kernel<CAUSAL, ROPE>, DQ_LDS),
+                              raise_lds(attn_gqa_dkv_kernel<CAUSAL, ROPE>, DKV_LDS), true);
     (void)attr;
     const int n = S / BK;
-    attn_gqa_dq_kernel<CAUSAL><<<B * a.H * n, 256, DQ_LDS, s>>>(a, dsum, Hkv, S);   // fills all [B, H, S] of dsum
-    attn_gqa_dkv_kernel<CAUSAL><<<B * Hkv * n, 256, DKV_LDS, s>>>(a, dsum, Hkv, S);  // reads them (stream order)
+    // the dQ kernel fills all [B, H, S] of dsum, the dK/dV kernel reads them (stream order)
+    attn_gqa_dq_kernel<CAUSAL, ROPE><<<B * a.H * n, 256, DQ_LDS, s>>>(a, dsum, Hkv, S, cos, sin);
+    attn_gqa_dkv_kernel<CAUSAL, ROPE><<<B * Hkv * n, 256, DKV_LDS, s>>>(a, dsum, Hkv, S, cos, sin);
 }
 
 }  // namespace
@@ -361,13 +399,20 @@ void launch_attention_gqa_forward(const uint16_t *qkv, uint16_t *out, float *lse
 
 void launch_attention_gqa_backward(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *dout,
                                    uint16_t *dqkv, float *dsum, int B, int S, int H, int Hkv, float scale,
-                                   uint32_t seed, float p_drop, bool causal, hipStream_t s) {
+                                   uint32_t seed, float p_drop, bool causal, hipStream_t s, const float *cos,
+                                   const float *sin) {
     check(S, H, Hkv);
+    if (!cos != !sin) throw std::invalid_argument("attention: the rotary tables cos and sin come together");
     if (!dsum) throw std::invalid_argument("attention: the grouped-query backward needs the [B, H, S] f32 dsum buffer");
     const AttnArgs a = make_args(qkv, const_cast<uint16_t *>(out), const_cast<float *>(lse), dout, dqkv, H, scale, seed,
                                  p_drop);
-    if (causal) backward<true>(a, dsum, Hkv, B, S, s);
-    else backward<false>(a, dsum, Hkv, B, S, s);
+    if (cos) {
+        if (causal) backward<true, true>(a, dsum, Hkv, B, S, cos, sin, s);
+        else backward<false, true>(a, dsum, Hkv, B, S, cos, sin, s);
+    } else {
+        if (causal) backward<true, false>(a, dsum, Hkv, B, S, nullptr, nullptr, s);
+        else backward<false, false>(a, dsum, Hkv, B, S, nullptr, nullptr, s);
+    }
 }
 
 }  // namespace kfk

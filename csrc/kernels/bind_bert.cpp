@@ -252,11 +252,38 @@ std::vector<at::Tensor> attention_gqa_forward(at::Tensor qkv, int64_t heads, int
     return {out, lse};
 }
 
+// A rotary table (attention_rope.hip): contiguous f32 [S, 64] on qkv's device
+const float *check_rope_table(const at::Tensor &t, const at::Tensor &qkv, const char *op, const char *name) {
+    TORCH_CHECK(t.scalar_type() == at::kFloat && t.dim() == 2 && t.size(0) == qkv.size(1) && t.size(1) == 64 &&
+                    t.is_contiguous() && t.device() == qkv.device(),
+                op, ": ", name, " must be a contiguous f32 [S, 64] table on qkv's device");
+    return t.data_ptr<float>();
+}
+
+// Rotary position embeddings ahead of the grouped-query kernels: qkv [B, S, (H + 2*Hkv)*128] -> the same layout with
+// the Q and K heads rotated (half-split convention, positions 0 .. S-1, f32, one rounding) and the V heads copied
+at::Tensor rope_forward(at::Tensor qkv, int64_t heads, int64_t kv_heads, at::Tensor cos, at::Tensor sin) {
+    const char *op = "rope_forward";
+    const auto [B, S, H, Hkv] = check_qkv_gqa(qkv, heads, kv_heads, op);
+    const float *c = check_rope_table(cos, qkv, op, "cos"), *s = check_rope_table(sin, qkv, op, "sin");
+    check_extent32(op, "the token count", {qkv.size(0), qkv.size(1)});
+    c10::DeviceGuard gd(qkv.device());
+    auto out = at::empty_like(qkv);
+    kfk::launch_rope_forward(bf16(qkv), bf16_mut(out), c, s, B, S, H, Hkv, stream_of(qkv, 0));
+    return out;
+}
+
 // -> dqkv in qkv's layout; dk / dv of a K/V head are the f32 sums over its group's query heads, rounded once
+// cos, sin (both or neither): qkv is rope_forward's result, and dq / dk come back as gradients of its input (the
+// transposed rotation in the kernels' epilogues, f32, ahead of the one rounding)
 at::Tensor attention_gqa_backward(at::Tensor qkv, at::Tensor out, at::Tensor lse, at::Tensor dout, int64_t heads,
-                                  int64_t kv_heads, double scale, int64_t seed, double p_drop, bool causal) {
+                                  int64_t kv_heads, double scale, int64_t seed, double p_drop, bool causal,
+                                  OptTensor cos, OptTensor sin) {
     const char *op = "attention_gqa_backward";
     const auto [B, S, H, Hkv] = check_qkv_gqa(qkv, heads, kv_heads, op);
+    TORCH_CHECK(has(cos) == has(sin), op, ": cos and sin must be given together, got only ", has(cos) ? "cos" : "sin");
+    const float *ct = has(cos) ? check_rope_table(*cos, qkv, op, "cos") : nullptr;
+    const float *st = has(sin) ? check_rope_table(*sin, qkv, op, "sin") : nullptr;
     const Dev dev = qkv.device();
     check_dense(out, op, "out", dev, at::kBFloat16, out.numel());
     TORCH_CHECK(out.sizes() == at::IntArrayRef({B, S, H * 128}),
@@ -273,7 +300,7 @@ at::Tensor attention_gqa_backward(at::Tensor qkv, at::Tensor out, at::Tensor lse
     kfk::launch_attention_gqa_backward(bf16(qkv), bf16(out), lse.data_ptr<float>(), bf16(dout), bf16_mut(dqkv),
                                        dsum.data_ptr<float>(), B, S, H, Hkv, static_cast<float>(scale),
                                        static_cast<uint32_t>(seed), static_cast<float>(p_drop), causal,
-                                       stream_of(qkv, 0));
+                                       stream_of(qkv, 0), ct, st);
     return dqkv;
 }
 
@@ -473,9 +500,17 @@ void bind_bert(py::module_ &m) {
           py::arg("qkv"), py::arg("heads"), py::arg("kv_heads"), py::arg("scale"), py::arg("seed"), py::arg("p_drop"),
           py::arg("causal") = false);
     m.def("attention_gqa_backward", &attention_gqa_backward,
-          "fused grouped-query self-attention backward -> dqkv in qkv's layout (dk / dv summed over each group in f32)",
+          "fused grouped-query self-attention backward -> dqkv in qkv's layout (dk / dv summed over each group in f32)"
+          "; cos, sin (f32 [S, 64], both or neither): qkv is rope_forward's result and dq / dk are rotated back in "
+          "the kernels' epilogues",
           py::arg("qkv"), py::arg("out"), py::arg("lse"), py::arg("dout"), py::arg("heads"), py::arg("kv_heads"),
-          py::arg("scale"), py::arg("seed"), py::arg("p_drop"), py::arg("causal") = false);
+          py::arg("scale"), py::arg("seed"), py::arg("p_drop"), py::arg("causal") = false, py::kw_only(),
+          py::arg("cos") = py::none(), py::arg("sin") = py::none());
+    m.def("rope_forward", &rope_forward,
+          "rotary position embeddings (half-split convention, positions 0 .. S-1) on the query and key heads of qkv "
+          "[B, S, (heads + 2*kv_heads)*128] from f32 [S, 64] tables -> the rotated tensor in qkv's layout (value heads "
+          "copied)",
+          py::arg("qkv"), py::arg("heads"), py::arg("kv_heads"), py::arg("cos"), py::arg("sin"));
     m.def("gemm_nt", &gemm_nt, py::arg("a"), py::arg("b"), py::arg("bias") = py::none(), py::arg("out") = py::none(),
           py::arg("accumulate") = false, py::arg("bn") = -1,
           "bf16 a[M,K] . b[N,K]^T (+bias) (+out) on the pipelined 256 x bn MFMA GEMM (gemm.hip)");

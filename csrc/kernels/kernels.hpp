@@ -538,11 +538,20 @@ void launch_attention_d128_backward(const uint16_t *qkv, const uint16_t *out, co
 // value heads of a row), out [B, S, H*128], lse and dsum [B, H, S]; S as above, bidirectional or causal, no lengths.
 // dK/dV are summed over a group's query heads in registers (one workgroup per K/V head and key block) and rounded once.
 // Hkv == H is attention_d128's layout and its results bit for bit.
+// cos / sin (both or neither; f32 [S, 64] on the device): qkv holds heads that launch_rope_forward rotated, and the
+// backward's dQ and dK/dV epilogues apply the transposed rotation to dq and dk in f32 before their one rounding.
 bool attention_gqa_supported(int S, int heads, int kv_heads);
 void launch_attention_gqa_forward(const uint16_t *qkv, uint16_t *out, float *lse, int B, int S, int H, int Hkv,
                                   float scale, uint32_t seed, float p_drop, bool causal, hipStream_t s);
 void launch_attention_gqa_backward(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *dout,
                                    uint16_t *dqkv, float *dsum, int B, int S, int H, int Hkv, float scale,
-                                   uint32_t seed, float p_drop, bool causal, hipStream_t s);
+                                   uint32_t seed, float p_drop, bool causal, hipStream_t s, const float *cos = nullptr,
+                                   const float *sin = nullptr);
+// Rotary position embeddings at head dim 128 (attention_rope.hip), half-split convention over the whole head,
+// positions 0 .. S - 1: out = qkv [B, S, (H + 2 Hkv) * 128] with the H query and Hkv key heads rotated by the f32
+// [S, 64] tables (x'[i] = x[i] cos - x[i + 64] sin, x'[i + 64] = x[i + 64] cos + x[i] sin, f32, rounded once) and the
+// value heads copied.  S, H, Hkv as attention_gqa_supported.
+void launch_rope_forward(const uint16_t *qkv, uint16_t *out, const float *cos, const float *sin, int B, int S, int H,
+                         int Hkv, hipStream_t s);
 
 }  // namespace kfk

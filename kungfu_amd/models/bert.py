@@ -10,7 +10,9 @@ decoder block of models/gpt.py: the causal fused kernels, with neither mask nor 
 ``d / heads``: 64 (BERT, GPT) and 128 (``BertLayer(1024, 8, 4096)``: csrc/kernels/attention_d128.hip, S up to 1024,
 no ``lengths``) have fused kernels, any other head dim runs scaled_dot_product_attention.
 ``BertLayer(..., kv_heads=Hkv)`` is grouped-query attention: one projection of ``heads + 2*Hkv`` heads, at head dim 128 on
-csrc/kernels/attention_gqa.hip (neither mask nor lengths)."""
+csrc/kernels/attention_gqa.hip (neither mask nor lengths).  ``BertLayer(..., rope=base)`` rotates Q and K by their
+positions (rotary embeddings, ops/attention.py; at head dim 128 fused into csrc/kernels/attention_rope.hip and the
+grouped-query backward); it takes no ``mask``."""
 import math
 
 import torch
@@ -25,11 +27,12 @@ from ..ops.linear import gelu, residual_link
 
 
 class BertLayer(nn.Module):
-    def __init__(self, d=768, heads=12, ffn=3072, dropout=0.1, kv_heads=None):
+    def __init__(self, d=768, heads=12, ffn=3072, dropout=0.1, kv_heads=None, rope=None):
         super().__init__()
         from ..ops.layernorm import AddLayerNorm
 
         self.heads = heads
+        self.rope = rope  # the base of rotary position embeddings on Q and K (ops/attention.py), or None
         # grouped-query heads: kv_heads K/V heads shared by heads / kv_heads query heads each, one projection of
         # (heads + 2 kv_heads) heads (ops/attention.py); None: as many K/V heads as query heads
         self.kv_heads = kv_heads
@@ -54,7 +57,11 @@ class BertLayer(nn.Module):
         # its gradient of x to the projection's data-gradient GEMM (ops.linear.ResidualLink)
         residual_link(x)
         qkv = self.qkv(x)
-        if self.kv_heads is not None:
+        if self.rope is not None:
+            if mask is not None:
+                raise ValueError("BertLayer: rope takes no mask")
+            a = self_attention(qkv, self.heads, p, lengths, causal, self.kv_heads, rope=self.rope)
+        elif self.kv_heads is not None:
             if mask is not None or lengths is not None:
                 raise ValueError("BertLayer: kv_heads takes neither mask nor lengths")
             a = self_attention(qkv, self.heads, p, causal=causal, kv_heads=self.kv_heads)

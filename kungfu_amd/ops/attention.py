@@ -54,9 +54,27 @@ registers and rounds once (profiles/attention_gqa.md).  The dropout hash stays k
 with ``lengths`` is a ``ValueError``.  Everything else (CPU, f32, other S, head dim 64, S > 128 with
 ``KUNGFU_ATTN_LONG=0``, the (mask, S, G) triples of ``_GQA_ROUTED_AWAY``, ``_GQA_ENABLED = False``) expands K/V over the
 group and runs ``F.scaled_dot_product_attention``; autograd sums the group's dk / dv.
+
+Rotary position embeddings (LLaMA 1/2/3, Mistral, Qwen, GPT-NeoX): ``self_attention(..., rope=base)`` (for instance
+``10000.0``) rotates every Q and K head by its position 0 .. S-1 before the scores, in the half-split ("rotate_half")
+convention over the whole head: with ``theta_i = base ** (-i / (dh/2))``, ``c = cos(t * theta_i)`` and
+``s = sin(t * theta_i)``, ``x'[i] = x[i]*c - x[i + dh/2]*s`` and ``x'[i + dh/2] = x[i + dh/2]*c + x[i]*s`` for
+``i < dh/2``; V is untouched.  (Meta's interleaved convention, pairs ``(2i, 2i + 1)``, is this one under a fixed
+permutation of the projection's output columns of each Q and K head; it is not implemented.)  ``cos`` and ``sin`` are
+f32 ``[S, dh/2]`` tables computed once in float64 and cached (:func:`rope_tables`).  At head dim 128, with or without
+``kv_heads``, on the domain of the grouped-query kernels (:func:`eligible_gqa` for ``kv_heads or heads``; multi-head
+attention runs them at G = 1, where they are the head dim 128 kernels bit for bit) one streaming kernel
+(csrc/kernels/attention_rope.hip) writes the rotated ``qkv`` once, in f32 with one rounding; the attention forward
+reads it and it is what the backward keeps.  The gradient's transposed rotation runs in f32 in the epilogues of the dQ
+and dK/dV kernels, ahead of their single rounding to bf16, so the backward has no pass over ``dqkv`` at all
+(profiles/attention_rope.md).  Every other call (CPU, f32, head dim 64, other S, ``lengths``, ``_ROPE_ENABLED = False``,
+the (mask, S, G) triples of ``_ROPE_ROUTED_AWAY``) rotates Q and K in torch, which autograd differentiates, and runs
+``self_attention`` on the result without ``rope``: every path above is reached that way.  A ``rope`` that is not
+positive and finite is a ``ValueError``; ``rope=None`` is the call without the keyword.
 """
 from __future__ import annotations
 
+import functools
 import math
 import os
 
@@ -186,6 +204,75 @@ def _gqa_attention(qkv: torch.Tensor, heads: int, kv_heads: int, p: float, causa
     return a.transpose(1, 2).reshape(B, S, heads * dh)
 
 
+@functools.lru_cache(maxsize=None)
+def _rope_tables(S: int, base: float, device: torch.device, half: int):
+    theta = base ** (-torch.arange(half, dtype=torch.float64) / half)
+    angle = torch.arange(S, dtype=torch.float64)[:, None] * theta[None]
+    return angle.cos().float().to(device).contiguous(), angle.sin().float().to(device).contiguous()
+
+
+def rope_tables(S: int, base: float, device, half: int = 64):
+    """``(cos, sin)``, f32 ``[S, half]`` on ``device``: ``cos(t * base ** (-i / half))`` for position ``t`` and pair
+    ``i``, evaluated in float64 (the angles reach S - 1 rad) and cached per (S, base, device, half).  The tables are
+    shared between calls: do not write to them."""
+    return _rope_tables(int(S), float(base), torch.device(device), int(half))
+
+
+class _AttnRopeFn(torch.autograd.Function):
+    """Rotary position embeddings at head dim 128: attention_rope.hip's rotation, then the kernels of
+    attention_gqa.hip on its result, whose backward rotates dq and dk back in its epilogues."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads, kv_heads, p, seed, causal, base):
+        scale = 1.0 / math.sqrt(128.0)
+        cos, sin = rope_tables(qkv.shape[1], base, qkv.device)
+        rot = hip().rope_forward(qkv, heads, kv_heads, cos, sin)
+        out, lse = hip().attention_gqa_forward(rot, heads, kv_heads, scale, seed, p, causal)
+        ctx.save_for_backward(rot, out, lse, cos, sin)  # the unrotated qkv is not kept
+        ctx.heads, ctx.kv_heads, ctx.p, ctx.seed, ctx.scale, ctx.causal = heads, kv_heads, p, seed, scale, causal
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        rot, out, lse, cos, sin = ctx.saved_tensors
+        dqkv = hip().attention_gqa_backward(rot, out, lse, dout.contiguous(), ctx.heads, ctx.kv_heads, ctx.scale,
+                                            ctx.seed, ctx.p, ctx.causal, cos=cos, sin=sin)
+        return dqkv, None, None, None, None, None, None
+
+
+# (causal, S, G) triples whose forward + backward with the fused rotation did not beat the better of the rotation
+# composed in torch around the fused kernels and around the SDPA path by more than the measured spread
+# (profiles/attention_rope.md): they keep the fallback
+_ROPE_ROUTED_AWAY: frozenset = frozenset()
+# False: every rope call rotates in torch (tests and tools/bench_attention.py compare the paths in one process)
+_ROPE_ENABLED = True
+
+
+def _rope_attention(qkv: torch.Tensor, heads: int, p: float, lengths, causal: bool, kv_heads, rope) -> torch.Tensor:
+    """``self_attention`` with ``rope``: the fused rotation where the grouped-query kernels serve the call, else the
+    rotation in torch around ``self_attention`` without ``rope``."""
+    if isinstance(rope, bool) or not isinstance(rope, (int, float)) or not (0.0 < rope < math.inf):
+        raise ValueError("self_attention: rope must be a positive finite base (for instance 10000.0), got %r" % (rope,))
+    Hkv = heads if kv_heads is None else kv_heads
+    B, S, W = qkv.shape
+    if Hkv < 1 or heads % Hkv or W % (2 * (heads + 2 * Hkv)):
+        raise ValueError("self_attention: rope needs kv_heads to divide heads and qkv's last dim to be "
+                         "(heads + 2*kv_heads) * dh with dh even, got %d for heads %d, kv_heads %d" % (W, heads, Hkv))
+    if (_ROPE_ENABLED and lengths is None and W == (heads + 2 * Hkv) * 128 and eligible_gqa(qkv, heads, Hkv, causal)
+            and (bool(causal), S, heads // Hkv) not in _ROPE_ROUTED_AWAY):
+        seed = int(torch.randint(0, 2**31 - 1, (1,)).item())  # CPU generator: no device sync
+        dropout_seed.base(qkv.device)
+        return _AttnRopeFn.apply(qkv, heads, Hkv, float(p), seed, bool(causal), float(rope))
+    dh = W // (heads + 2 * Hkv)
+    cos, sin = (t[None, :, None, :] for t in rope_tables(S, rope, qkv.device, dh // 2))
+    x = qkv.view(B, S, heads + 2 * Hkv, dh)
+    qk, v = x[:, :, :heads + Hkv], x[:, :, heads + Hkv:]
+    # in f32 (f64 for f64 inputs) with one rounding, as the kernel
+    x1, x2 = qk.to(torch.promote_types(qkv.dtype, torch.float32)).split(dh // 2, dim=3)
+    rot = torch.cat((x1 * cos - x2 * sin, x2 * cos + x1 * sin), dim=3).to(qkv.dtype)
+    return self_attention(torch.cat((rot, v), dim=2).view(B, S, W), heads, p, lengths, causal, kv_heads)
+
+
 def eligible(qkv: torch.Tensor, heads: int, lengths=None, causal: bool = False) -> bool:
     """Whether the fused kernels serve this call; with ``lengths`` only the streaming family does
     (S >= 128, and not with ``KUNGFU_ATTN_LONG=0``); ``causal``: S a multiple of 64 up to 1024, no lengths."""
@@ -224,14 +311,17 @@ def _lengths_fallback(qkv: torch.Tensor, heads: int, p: float, lengths: torch.Te
 
 
 def self_attention(qkv: torch.Tensor, heads: int, p: float = 0.0, lengths: torch.Tensor | None = None,
-                   causal: bool = False, kv_heads: int | None = None) -> torch.Tensor:
+                   causal: bool = False, kv_heads: int | None = None, rope: float | None = None) -> torch.Tensor:
     """softmax(Q K^T / sqrt(dh)) V with dropout ``p`` on the probabilities, per head (dh = 64 or 128 fused);
     ``qkv``: [B, S, 3*H*dh] -> [B, S, H*dh].  ``lengths`` (int32 [B], on qkv's device): the valid
     tokens of each padded sequence; ``causal``: query q attends to keys <= q; ``kv_heads``: grouped-query heads,
-    ``qkv`` [B, S, (H + 2*kv_heads)*dh] (module docstring)."""
+    ``qkv`` [B, S, (H + 2*kv_heads)*dh]; ``rope``: the base of rotary position embeddings on Q and K (module
+    docstring)."""
     B, S, D3 = qkv.shape
     if causal and lengths is not None:
         raise ValueError("self_attention: causal attention takes no lengths: right padding cannot reach a valid row")
+    if rope is not None:
+        return _rope_attention(qkv, heads, p, lengths, causal, kv_heads, rope)
     if kv_heads is not None:
         if kv_heads < 1 or heads % kv_heads:
             raise ValueError("self_attention: kv_heads must be at least 1 and divide heads, got heads %d, kv_heads %d"

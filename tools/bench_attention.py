@@ -25,8 +25,12 @@ With ``--head-dim 128 --kv-heads N`` it times the grouped-query kernels (attenti
 serve the call without them: K/V expanded for the head dim 128 kernels plus the group sum of dk / dv, and the SDPA
 fallback.
 
+With ``--head-dim 128 --rope BASE`` (with or without ``--kv-heads``) it times ``self_attention(..., rope=BASE)``:
+the fused rotation (attention_rope.hip and the grouped-query backward's epilogues) against the rotation in torch
+around the fused kernels and around SDPA, and the rotation kernel alone.
+
     python tools/bench_attention.py [calls] [--batch 128] [--seq 128] [--heads 12] [--lengths 0.5|random] [--causal]
-                                    [--head-dim 64|128] [--kv-heads N]"""
+                                    [--head-dim 64|128] [--kv-heads N] [--rope BASE]"""
 import argparse
 import os
 import sys
@@ -261,6 +265,74 @@ def gqa(args, H):
             c, S, B, G, p, m["gqa"] / m["expand"], m["gqa"] / m["sdpa"], m["gqa again"] / m["gqa"]), flush=True)
 
 
+def rope(args, H):
+    """Rotary position embeddings at head dim 128 (``--rope BASE``, with or without ``--kv-heads``): forward and
+    backward time of ``self_attention(..., rope=BASE)`` on its three routes, the variants alternating over the rounds:
+    ``rope`` (attention_rope.hip, the grouped-query forward on its result, the backward with the rotation in its
+    epilogues; twice per round: ``rope again`` / ``rope`` is the run-to-run spread), ``torch+fused`` (``_ROPE_ENABLED =
+    False``: Q and K rotated in torch around the fused kernels, autograd rotating dqkv back) and ``torch+sdpa`` (the
+    fused attention switched off as well).  Then the rotation kernel alone with its bytes/s against a 5.3 TB/s
+    streaming roofline, and with ``kv_heads == heads`` the grouped-query kernels at G = 1 against attention_d128.hip's,
+    both without rotation."""
+    B, S, NH, c, base = args.batch, args.seq, args.heads, args.causal, args.rope
+    NKV = NH if args.kv_heads is None else args.kv_heads
+    G, scale, kv = NH // NKV, 128 ** -0.5, args.kv_heads
+    torch.manual_seed(0)
+    qkv = (torch.randn(B, S, (NH + 2 * NKV) * 128, device="cuda") * 0.5).bfloat16()
+    dout = (torch.randn(B, S, NH * 128, device="cuda") * 0.1).bfloat16()
+    cos, sin = attn.rope_tables(S, base, qkv.device)
+    switches = {"rope": {}, "torch+fused": {"_ROPE_ENABLED": False},
+                "torch+sdpa": {"_ROPE_ENABLED": False, "_GQA_ENABLED": False, "_D128_ENABLED": False}}
+    fused_fns = ("_AttnRopeFnBackward", "_AttnGQAFnBackward", "_AttnD128FnBackward")
+
+    def route(name, q, p):
+        for k, v in switches[name].items():
+            setattr(attn, k, v)
+        try:
+            return attn.self_attention(q, NH, p, causal=c, kv_heads=kv, rope=base)
+        finally:
+            for k in switches[name]:
+                setattr(attn, k, True)
+
+    tag = "causal=%d S=%d B=%d G=%d" % (c, S, B, G)
+    for p in (0.1, 0.0):
+        variants = {}
+        for name in switches:
+            q = qkv.clone().requires_grad_(True)
+            y = route(name, q, p)
+            assert (type(y.grad_fn).__name__ == fused_fns[0]) == (name == "rope"), (name, y.grad_fn)
+            assert name != "torch+sdpa" or type(y.grad_fn).__name__ not in fused_fns, y.grad_fn
+            variants[name] = (lambda name=name, q=q: route(name, q, p),
+                              lambda y=y, q=q: torch.autograd.grad(y, q, dout, retain_graph=True))
+        variants = {"rope": variants["rope"], "rope again": variants["rope"], "torch+fused": variants["torch+fused"],
+                    "torch+sdpa": variants["torch+sdpa"]}
+        if G == 1:
+            out, lse = H.attention_d128_forward(qkv, NH, scale, 1234, p, c)
+            variants["plain d128"] = (lambda: H.attention_d128_forward(qkv, NH, scale, 1234, p, c),
+                                      lambda: H.attention_d128_backward(qkv, out, lse, dout, NH, scale, 1234, p, c))
+            variants["plain gqa"] = (lambda: H.attention_gqa_forward(qkv, NH, NH, scale, 1234, p, c),
+                                     lambda: H.attention_gqa_backward(qkv, out, lse, dout, NH, NH, scale, 1234, p, c))
+        ts = {k: [] for k in variants}
+        for _ in range(args.rounds):
+            for k, (f, b) in variants.items():
+                ts[k].append((med(f, args.calls), med(b, args.calls)))
+        m = {}
+        for k, v in ts.items():
+            fs, bs, tot = sorted(f for f, _ in v), sorted(b for _, b in v), sorted(f + b for f, b in v)
+            m[k] = tot[len(tot) // 2]
+            print("%s p=%.1f  %-11s fwd %7.1f us  bwd %7.1f us  fwd+bwd %7.1f us (min %7.1f max %7.1f) over %d rounds" % (
+                tag, p, k, fs[len(fs) // 2], bs[len(bs) // 2], m[k], tot[0], tot[-1], len(v)), flush=True)
+        line = "%s p=%.1f  fwd+bwd: rope / torch+fused %.3f   rope / torch+sdpa %.3f   rope again / rope %.3f" % (
+            tag, p, m["rope"] / m["torch+fused"], m["rope"] / m["torch+sdpa"], m["rope again"] / m["rope"])
+        if G == 1:
+            line += "   plain gqa / plain d128 %.3f" % (m["plain gqa"] / m["plain d128"])
+        print(line, flush=True)
+    rs = sorted(med(lambda: H.rope_forward(qkv, NH, NKV, cos, sin), args.calls) for _ in range(args.rounds))
+    t, nbytes = rs[len(rs) // 2], 2 * qkv.numel() * 2 + 2 * cos.numel() * 4  # qkv read and written once, the tables once
+    print("%s rope_forward alone %7.1f us (min %7.1f max %7.1f): %.2f TB/s of %d bytes, %.0f %% of 5.3 TB/s" % (
+        tag, t, rs[0], rs[-1], nbytes / t / 1e6, nbytes, 100 * nbytes / 5.3e6 / t), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("calls", nargs="?", type=int, default=20, help="calls to time")
@@ -276,10 +348,18 @@ def main():
     ap.add_argument("--kv-heads", type=int, default=None,
                     help="grouped-query heads (needs --head-dim 128): the attention_gqa.hip kernels against the "
                          "expanded-K/V attention_d128.hip path and SDPA")
+    ap.add_argument("--rope", type=float, default=None, metavar="BASE",
+                    help="rotary position embeddings of this base (needs --head-dim 128, with or without --kv-heads): "
+                         "the fused rotation against the rotation in torch around the fused kernels and around SDPA")
     args = ap.parse_args()
     n = args.calls
     H = hip()
     B, S, NH = args.batch, args.seq, args.heads
+    if args.rope is not None:
+        if args.head_dim != 128 or (args.kv_heads is not None and (args.kv_heads < 1 or NH % args.kv_heads)):
+            ap.error("--rope needs --head-dim 128 and, if given, --kv-heads a divisor of --heads")
+        print("B=%d S=%d H=%d Hkv=%s rope=%g" % (B, S, NH, args.kv_heads, args.rope), flush=True)
+        return rope(args, H)
     if args.kv_heads is not None:
         if args.head_dim != 128 or args.kv_heads < 1 or NH % args.kv_heads:
             ap.error("--kv-heads needs --head-dim 128 and a divisor of --heads")
