@@ -48,12 +48,6 @@
 
 #include <stdexcept>
 
-#if defined(__HIP_DEVICE_COMPILE__)
-#define KFK_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
-#else
-#define KFK_NO_PK_F32
-#endif
-
 namespace kfk {
 
 namespace {

@@ -1,6 +1,6 @@
 // Rotary position embeddings (RoPE) for the head dim 128 attention kernels: the forward rotation of the Q and K heads
-// of a grouped-query qkv tensor, one streaming pass.  Its output is what attention_gqa.hip's forward reads and what is
-// saved for the backward; the transposed rotation of dq / dk runs in the epilogues of attention_gqa.hip's dQ and dK/dV
+// of a grouped-query qkv tensor, one streaming pass.  Its output is what attention_d128.hip's forward reads and what is
+// saved for the backward; the transposed rotation of dq / dk runs in the epilogues of attention_d128.hip's dQ and dK/dV
 // kernels (template parameter ROPE there), so the backward has no pass of its own.
 //
 // Convention   Half-split ("rotate_half": Hugging Face LLaMA, GPT-NeoX) over the whole head, positions 0 .. S - 1.
@@ -28,16 +28,9 @@
 //   cos, sin      row t = tok mod S < S, floats 8 j .. 8 j + 7 <= 63.
 //
 // Compiled without packed f32 instructions (KFK_NO_PK_F32), the precaution attention_lengths.hip's header explains.
-#include "common.hpp"
-#include "kernels.hpp"
+#include "attention_common.hpp"
 
 #include <stdexcept>
-
-#if defined(__HIP_DEVICE_COMPILE__)
-#define KFK_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
-#else
-#define KFK_NO_PK_F32
-#endif
 
 namespace kfk {
 

@@ -177,7 +177,8 @@ at::Tensor attention_backward(at::Tensor qkv, at::Tensor out, at::Tensor lse, at
     return dqkv;
 }
 
-// Head dim 128 (attention_d128.hip): contiguous bf16 [B, S, 3*H*128] with S a multiple of 64 up to 1024: {B, S, H}
+// Head dim 128 (attention_d128.hip), multi-head: contiguous bf16 [B, S, 3*H*128] with S a multiple of 64 up to 1024:
+// {B, S, H}
 std::tuple<int, int, int> check_qkv_d128(const at::Tensor &qkv, int64_t heads, const char *op) {
     check_dense(qkv, op, "qkv", kAnyGpu, at::kBFloat16, qkv.numel());
     TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == 3 * heads * 128 && qkv.size(1) <= 1024 &&
@@ -186,45 +187,57 @@ std::tuple<int, int, int> check_qkv_d128(const at::Tensor &qkv, int64_t heads, c
     return {narrow(qkv.size(0), op, "B"), narrow(qkv.size(1), op, "S"), narrow(heads, op, "heads")};
 }
 
-// Fused self-attention at head dim 128: qkv [B, S, 3*H*128] bf16 contiguous -> (out [B, S, H*128] bf16, lse [B, H, S]
-// f32); causal: query q sees keys <= q.  No lengths at this head dim.
-std::vector<at::Tensor> attention_d128_forward(at::Tensor qkv, int64_t heads, double scale, int64_t seed, double p_drop,
-                                               bool causal) {
-    const auto [B, S, H] = check_qkv_d128(qkv, heads, "attention_d128_forward");
+// The head dim 128 kernels on a checked qkv [B, S, (H + 2*Hkv)*128] -> (out [B, S, H*128] bf16, lse [B, H, S] f32)
+std::vector<at::Tensor> d128_forward(const at::Tensor &qkv, int B, int S, int H, int Hkv, double scale, int64_t seed,
+                                     double p_drop, bool causal) {
     c10::DeviceGuard gd(qkv.device());
     auto out = at::empty({B, S, H * 128}, qkv.options());
     auto lse = at::empty({B, H, S}, qkv.options().dtype(at::kFloat));
-    kfk::launch_attention_d128_forward(bf16(qkv), bf16_mut(out), lse.data_ptr<float>(), B, S, H,
-                                       static_cast<float>(scale), static_cast<uint32_t>(seed),
-                                       static_cast<float>(p_drop), causal, stream_of(qkv, 0));
+    kfk::launch_attention_gqa_forward(bf16(qkv), bf16_mut(out), lse.data_ptr<float>(), B, S, H, Hkv,
+                                      static_cast<float>(scale), static_cast<uint32_t>(seed),
+                                      static_cast<float>(p_drop), causal, stream_of(qkv, 0));
     return {out, lse};
+}
+
+// Their backward for the binding `op`: checks out, dout and lse against the checked qkv -> dqkv in qkv's layout
+// (cos, sin: the checked rotary tables, or both null)
+at::Tensor d128_backward(const char *op, const at::Tensor &qkv, const at::Tensor &out, const at::Tensor &lse,
+                         at::Tensor dout, int B, int S, int H, int Hkv, double scale, int64_t seed, double p_drop,
+                         bool causal, const float *cos, const float *sin) {
+    const Dev dev = qkv.device();
+    check_dense(out, op, "out", dev, at::kBFloat16, out.numel());
+    TORCH_CHECK(out.sizes() == at::IntArrayRef({B, S, H * 128}), op, ": out must be the forward's [B, S, H*128] output");
+    TORCH_CHECK(dout.sizes() == out.sizes() && dout.scalar_type() == at::kBFloat16 && dout.device() == qkv.device(), op,
+                ": dout must be bf16 of out's shape on qkv's device");
+    check_dense(lse, op, "lse", dev, at::kFloat, lse.numel());
+    TORCH_CHECK(lse.sizes() == at::IntArrayRef({B, H, S}), op, ": lse must be the forward's [B, H, S] f32");
+    c10::DeviceGuard gd(qkv.device());
+    if (!dout.is_contiguous()) dout = dout.contiguous();
+    auto dqkv = at::empty_like(qkv);
+    auto dsum = at::empty({B, H, S}, lse.options());  // the dQ kernel fills it for the dK/dV kernel
+    kfk::launch_attention_gqa_backward(bf16(qkv), bf16(out), lse.data_ptr<float>(), bf16(dout), bf16_mut(dqkv),
+                                       dsum.data_ptr<float>(), B, S, H, Hkv, static_cast<float>(scale),
+                                       static_cast<uint32_t>(seed), static_cast<float>(p_drop), causal,
+                                       stream_of(qkv, 0), cos, sin);
+    return dqkv;
+}
+
+// Fused self-attention at head dim 128: qkv [B, S, 3*H*128] bf16 contiguous -> (out [B, S, H*128] bf16, lse [B, H, S]
+// f32); causal: query q sees keys <= q.  No lengths at this head dim.  The grouped-query kernels with Hkv = H.
+std::vector<at::Tensor> attention_d128_forward(at::Tensor qkv, int64_t heads, double scale, int64_t seed, double p_drop,
+                                               bool causal) {
+    const auto [B, S, H] = check_qkv_d128(qkv, heads, "attention_d128_forward");
+    return d128_forward(qkv, B, S, H, H, scale, seed, p_drop, causal);
 }
 
 at::Tensor attention_d128_backward(at::Tensor qkv, at::Tensor out, at::Tensor lse, at::Tensor dout, int64_t heads,
                                    double scale, int64_t seed, double p_drop, bool causal) {
     const char *op = "attention_d128_backward";
     const auto [B, S, H] = check_qkv_d128(qkv, heads, op);
-    const Dev dev = qkv.device();
-    check_dense(out, op, "out", dev, at::kBFloat16, out.numel());
-    TORCH_CHECK(out.sizes() == at::IntArrayRef({B, S, H * 128}),
-                "attention_d128_backward: out must be the forward's [B, S, H*128] output");
-    TORCH_CHECK(dout.sizes() == out.sizes() && dout.scalar_type() == at::kBFloat16 && dout.device() == qkv.device(),
-                "attention_d128_backward: dout must be bf16 of out's shape on qkv's device");
-    check_dense(lse, op, "lse", dev, at::kFloat, lse.numel());
-    TORCH_CHECK(lse.sizes() == at::IntArrayRef({B, H, S}),
-                "attention_d128_backward: lse must be the forward's [B, H, S] f32");
-    c10::DeviceGuard gd(qkv.device());
-    if (!dout.is_contiguous()) dout = dout.contiguous();
-    auto dqkv = at::empty_like(qkv);
-    auto dsum = at::empty({B, H, S}, lse.options());  // the dQ kernel fills it for the dK/dV kernel
-    kfk::launch_attention_d128_backward(bf16(qkv), bf16(out), lse.data_ptr<float>(), bf16(dout), bf16_mut(dqkv),
-                                        dsum.data_ptr<float>(), B, S, H, static_cast<float>(scale),
-                                        static_cast<uint32_t>(seed), static_cast<float>(p_drop), causal,
-                                        stream_of(qkv, 0));
-    return dqkv;
+    return d128_backward(op, qkv, out, lse, dout, B, S, H, H, scale, seed, p_drop, causal, nullptr, nullptr);
 }
 
-// Grouped-query heads at head dim 128 (attention_gqa.hip): contiguous bf16 [B, S, (H + 2*Hkv)*128] with H % Hkv == 0
+// Grouped-query heads at head dim 128 (attention_d128.hip): contiguous bf16 [B, S, (H + 2*Hkv)*128] with H % Hkv == 0
 // and S a multiple of 64 up to 1024: {B, S, H, Hkv}
 std::tuple<int, int, int, int> check_qkv_gqa(const at::Tensor &qkv, int64_t heads, int64_t kv_heads, const char *op) {
     TORCH_CHECK(kv_heads >= 1 && heads >= kv_heads && heads % kv_heads == 0, op,
@@ -243,13 +256,7 @@ std::tuple<int, int, int, int> check_qkv_gqa(const at::Tensor &qkv, int64_t head
 std::vector<at::Tensor> attention_gqa_forward(at::Tensor qkv, int64_t heads, int64_t kv_heads, double scale,
                                               int64_t seed, double p_drop, bool causal) {
     const auto [B, S, H, Hkv] = check_qkv_gqa(qkv, heads, kv_heads, "attention_gqa_forward");
-    c10::DeviceGuard gd(qkv.device());
-    auto out = at::empty({B, S, H * 128}, qkv.options());
-    auto lse = at::empty({B, H, S}, qkv.options().dtype(at::kFloat));
-    kfk::launch_attention_gqa_forward(bf16(qkv), bf16_mut(out), lse.data_ptr<float>(), B, S, H, Hkv,
-                                      static_cast<float>(scale), static_cast<uint32_t>(seed),
-                                      static_cast<float>(p_drop), causal, stream_of(qkv, 0));
-    return {out, lse};
+    return d128_forward(qkv, B, S, H, Hkv, scale, seed, p_drop, causal);
 }
 
 // A rotary table (attention_rope.hip): contiguous f32 [S, 64] on qkv's device
@@ -284,24 +291,7 @@ at::Tensor attention_gqa_backward(at::Tensor qkv, at::Tensor out, at::Tensor lse
     TORCH_CHECK(has(cos) == has(sin), op, ": cos and sin must be given together, got only ", has(cos) ? "cos" : "sin");
     const float *ct = has(cos) ? check_rope_table(*cos, qkv, op, "cos") : nullptr;
     const float *st = has(sin) ? check_rope_table(*sin, qkv, op, "sin") : nullptr;
-    const Dev dev = qkv.device();
-    check_dense(out, op, "out", dev, at::kBFloat16, out.numel());
-    TORCH_CHECK(out.sizes() == at::IntArrayRef({B, S, H * 128}),
-                "attention_gqa_backward: out must be the forward's [B, S, H*128] output");
-    TORCH_CHECK(dout.sizes() == out.sizes() && dout.scalar_type() == at::kBFloat16 && dout.device() == qkv.device(),
-                "attention_gqa_backward: dout must be bf16 of out's shape on qkv's device");
-    check_dense(lse, op, "lse", dev, at::kFloat, lse.numel());
-    TORCH_CHECK(lse.sizes() == at::IntArrayRef({B, H, S}),
-                "attention_gqa_backward: lse must be the forward's [B, H, S] f32");
-    c10::DeviceGuard gd(qkv.device());
-    if (!dout.is_contiguous()) dout = dout.contiguous();
-    auto dqkv = at::empty_like(qkv);
-    auto dsum = at::empty({B, H, S}, lse.options());  // the dQ kernel fills it for the dK/dV kernel
-    kfk::launch_attention_gqa_backward(bf16(qkv), bf16(out), lse.data_ptr<float>(), bf16(dout), bf16_mut(dqkv),
-                                       dsum.data_ptr<float>(), B, S, H, Hkv, static_cast<float>(scale),
-                                       static_cast<uint32_t>(seed), static_cast<float>(p_drop), causal,
-                                       stream_of(qkv, 0), ct, st);
-    return dqkv;
+    return d128_backward(op, qkv, out, lse, dout, B, S, H, Hkv, scale, seed, p_drop, causal, ct, st);
 }
 
 // y, s, mean, rstd = layernorm(x [+ r]) over the last dim (bf16 rows, f32 affine)

@@ -524,22 +524,16 @@ void launch_attention_backward(const uint16_t *qkv, const uint16_t *out, const f
                                uint16_t *dqkv, int B, int S, int H, float scale, uint32_t seed, float p_drop,
                                hipStream_t s, float *dsum = nullptr, bool stream_kernel = false,
                                const int *lengths = nullptr, bool causal = false, bool plain_order = false);
-// Head dim 128 (attention_d128.hip): the same interface with qkv [B, S, 3, H, 128], out [B, S, H*128], every S that
-// is a multiple of 64 from 64 to 1024, bidirectional or causal; no lengths.  Kernels of their own (256-byte LDS rows,
-// Q in registers, dynamic LDS): nothing of the 64-wide family above is launched.  dsum is always needed.
-bool attention_d128_supported(int S);
-void launch_attention_d128_forward(const uint16_t *qkv, uint16_t *out, float *lse, int B, int S, int H, float scale,
-                                   uint32_t seed, float p_drop, bool causal, hipStream_t s);
-void launch_attention_d128_backward(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *dout,
-                                    uint16_t *dqkv, float *dsum, int B, int S, int H, float scale, uint32_t seed,
-                                    float p_drop, bool causal, hipStream_t s);
-// Grouped-query attention at head dim 128 (attention_gqa.hip): H query heads share Hkv = H / G key/value heads, query
-// head h reads K/V head h / G.  qkv and dqkv [B, S, (H + 2 Hkv) * 128] (the H query heads, the Hkv key heads, the Hkv
-// value heads of a row), out [B, S, H*128], lse and dsum [B, H, S]; S as above, bidirectional or causal, no lengths.
-// dK/dV are summed over a group's query heads in registers (one workgroup per K/V head and key block) and rounded once.
-// Hkv == H is attention_d128's layout and its results bit for bit.
+// Head dim 128 (attention_d128.hip), multi-head and grouped-query: H query heads share Hkv = H / G key/value heads,
+// query head h reads K/V head h / G.  qkv and dqkv [B, S, (H + 2 Hkv) * 128] (the H query heads, the Hkv key heads, the
+// Hkv value heads of a row), out [B, S, H*128], lse and dsum [B, H, S]; every S that is a multiple of 64 from 64 to
+// 1024 (attention_d128_supported), bidirectional or causal; no lengths; dsum is always needed.  Kernels of their own
+// (256-byte LDS rows, Q in registers, dynamic LDS): nothing of the 64-wide family above is launched.  Multi-head
+// attention on qkv [B, S, 3, H, 128] is the call with Hkv == H.  dK/dV are summed over a group's query heads in
+// registers (one workgroup per K/V head and key block) and rounded once.
 // cos / sin (both or neither; f32 [S, 64] on the device): qkv holds heads that launch_rope_forward rotated, and the
 // backward's dQ and dK/dV epilogues apply the transposed rotation to dq and dk in f32 before their one rounding.
+bool attention_d128_supported(int S);
 bool attention_gqa_supported(int S, int heads, int kv_heads);
 void launch_attention_gqa_forward(const uint16_t *qkv, uint16_t *out, float *lse, int B, int S, int H, int Hkv,
                                   float scale, uint32_t seed, float p_drop, bool causal, hipStream_t s);

@@ -10,7 +10,7 @@ decoder block of models/gpt.py: the causal fused kernels, with neither mask nor 
 ``d / heads``: 64 (BERT, GPT) and 128 (``BertLayer(1024, 8, 4096)``: csrc/kernels/attention_d128.hip, S up to 1024,
 no ``lengths``) have fused kernels, any other head dim runs scaled_dot_product_attention.
 ``BertLayer(..., kv_heads=Hkv)`` is grouped-query attention: one projection of ``heads + 2*Hkv`` heads, at head dim 128 on
-csrc/kernels/attention_gqa.hip (neither mask nor lengths).  ``BertLayer(..., rope=base)`` rotates Q and K by their
+the same kernels, of which multi-head attention is the case ``Hkv == heads`` (neither mask nor lengths).  ``BertLayer(..., rope=base)`` rotates Q and K by their
 positions (rotary embeddings, ops/attention.py; at head dim 128 fused into csrc/kernels/attention_rope.hip and the
 grouped-query backward); it takes no ``mask``."""
 import math

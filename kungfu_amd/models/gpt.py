@@ -5,7 +5,7 @@ with ``causal=True``, whose attention runs the triangular fused HIP kernels of o
 of 64 up to 1024; anything else ``F.scaled_dot_product_attention(is_causal=True)``).  The head dim is ``d / heads``:
 64 and 128 have fused kernels.  ``gpt_d128`` is the same model with GPT-3 / LLaMA-style heads of 128: d = 1024, 8 heads,
 FFN 4096, whose attention runs csrc/kernels/attention_d128.hip; ``gpt_gqa`` is ``gpt_d128`` with LLaMA-2-style
-grouped-query attention (``kv_heads=2``: csrc/kernels/attention_gqa.hip); ``gpt_rope`` is ``gpt_gqa`` with rotary
+grouped-query attention (``kv_heads=2``: the same kernels with groups of 4 heads); ``gpt_rope`` is ``gpt_gqa`` with rotary
 position embeddings of base 10000 on Q and K instead of the learned position table (``rope=10000.0``: the LLaMA-2
 attention block; csrc/kernels/attention_rope.hip and the grouped-query backward's epilogues)."""
 import torch

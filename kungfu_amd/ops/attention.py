@@ -36,7 +36,8 @@ S > 128 with ``KUNGFU_ATTN_LONG=0``) is ``F.scaled_dot_product_attention(..., is
 Head dim 128 (GPT-3 from 6.7 B up, the LLaMA family): the head dim is ``qkv.shape[2] // (3 * heads)``, and at 128
 ``[B, S, 3*H*128]`` runs the kernels of csrc/kernels/attention_d128.hip, bidirectional or ``causal``, for every S that
 is a multiple of 64 from 64 to 1024: 256-byte LDS rows, the wave's Q rows in registers, 8 accumulator tiles, scale
-1 / sqrt(128), the same layouts, dropout hash and bitwise reproducibility (profiles/attention_d128.md).  There is no
+1 / sqrt(128), the same layouts, dropout hash and bitwise reproducibility (profiles/attention_d128.md).  They are one
+family with the grouped-query kernels below: multi-head attention is their instance with one head per group.  There is no
 ``lengths`` support at this head dim: head dim 128 with ``lengths`` runs :func:`_lengths_fallback`, and any other S, a
 CPU or f32 tensor, S > 128 with ``KUNGFU_ATTN_LONG=0`` and the (mask, S) pairs of ``_D128_ROUTED_AWAY`` run
 ``F.scaled_dot_product_attention``.  Other head dims always do.  The module switch ``_D128_ENABLED = False`` sends
@@ -47,8 +48,8 @@ Grouped-query attention (LLaMA-2 70B and later; one K/V head: multi-query attent
 the output of one ``nn.Linear(d, (H + 2*Hkv)*dh)``: the H query heads, then the Hkv key heads, then the Hkv value
 heads.  Query head ``h`` reads K/V head ``h // (H // Hkv)``; the result is ``[B, S, H*dh]`` and the gradient one tensor in
 the input's layout.  ``kv_heads=None`` or ``kv_heads == heads`` is the call without the keyword, through the paths
-above.  At head dim 128 the kernels of csrc/kernels/attention_gqa.hip serve the domain of the head dim 128 kernels
-(bf16, contiguous, S a multiple of 64 from 64 to 1024, either mask): K and V are never expanded, the G workgroups that
+above.  At head dim 128 the kernels of csrc/kernels/attention_d128.hip serve grouped heads on the domain of multi-head
+attention (bf16, contiguous, S a multiple of 64 from 64 to 1024, either mask): K and V are never expanded, the G workgroups that
 share a K/V head are dispatched next to each other, and the dK/dV kernel sums a group's query heads in its f32
 registers and rounds once (profiles/attention_gqa.md).  The dropout hash stays keyed on the query head.  ``kv_heads``
 with ``lengths`` is a ``ValueError``.  Everything else (CPU, f32, other S, head dim 64, S > 128 with
@@ -63,7 +64,7 @@ convention over the whole head: with ``theta_i = base ** (-i / (dh/2))``, ``c = 
 permutation of the projection's output columns of each Q and K head; it is not implemented.)  ``cos`` and ``sin`` are
 f32 ``[S, dh/2]`` tables computed once in float64 and cached (:func:`rope_tables`).  At head dim 128, with or without
 ``kv_heads``, on the domain of the grouped-query kernels (:func:`eligible_gqa` for ``kv_heads or heads``; multi-head
-attention runs them at G = 1, where they are the head dim 128 kernels bit for bit) one streaming kernel
+attention runs them at G = 1, as it does without ``rope``) one streaming kernel
 (csrc/kernels/attention_rope.hip) writes the rotated ``qkv`` once, in f32 with one rounding; the attention forward
 reads it and it is what the backward keeps.  The gradient's transposed rotation runs in f32 in the epilogues of the dQ
 and dK/dV kernels, ahead of their single rounding to bf16, so the backward has no pass over ``dqkv`` at all
@@ -114,7 +115,7 @@ class _AttnFn(torch.autograd.Function):
 
 
 class _AttnD128Fn(torch.autograd.Function):
-    """Head dim 128: the kernels of attention_d128.hip."""
+    """Head dim 128, multi-head: the kernels of attention_d128.hip with one head per group."""
 
     @staticmethod
     def forward(ctx, qkv, heads, p, seed, causal):
@@ -150,7 +151,7 @@ def eligible_d128(qkv: torch.Tensor, heads: int, lengths=None, causal: bool = Fa
 
 
 class _AttnGQAFn(torch.autograd.Function):
-    """Grouped-query heads at head dim 128: the kernels of attention_gqa.hip."""
+    """Grouped-query heads at head dim 128: the kernels of attention_d128.hip."""
 
     @staticmethod
     def forward(ctx, qkv, heads, kv_heads, p, seed, causal):
@@ -220,7 +221,7 @@ def rope_tables(S: int, base: float, device, half: int = 64):
 
 class _AttnRopeFn(torch.autograd.Function):
     """Rotary position embeddings at head dim 128: attention_rope.hip's rotation, then the kernels of
-    attention_gqa.hip on its result, whose backward rotates dq and dk back in its epilogues."""
+    attention_d128.hip on its result, whose backward rotates dq and dk back in its epilogues."""
 
     @staticmethod
     def forward(ctx, qkv, heads, kv_heads, p, seed, causal, base):

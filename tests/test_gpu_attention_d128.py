@@ -1,5 +1,5 @@
-"""GPU tests of the head dim 128 attention kernels (csrc/kernels/attention_d128.hip): bidirectional and causal,
-S = 64 .. 1024.
+"""GPU tests of the head dim 128 attention kernels (csrc/kernels/attention_d128.hip) on multi-head attention, their
+instance with one head per group (the ``attention_d128_*`` bindings): bidirectional and causal, S = 64 .. 1024.
 
 The reference is the float64 torch composition from the bf16 inputs (scale 1 / sqrt(128), the kernels' own dropout
 mask); the yardstick is the same composition evaluated on bf16 tensors.  Errors are relative L2 per (sequence, head,

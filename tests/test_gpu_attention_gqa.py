@@ -1,5 +1,5 @@
-"""GPU tests of the grouped-query attention kernels (csrc/kernels/attention_gqa.hip): head dim 128, qkv
-[B, S, (H + 2*Hkv)*128], bidirectional and causal, S = 64 .. 1024.
+"""GPU tests of the head dim 128 attention kernels (csrc/kernels/attention_d128.hip) on grouped-query heads (the
+``attention_gqa_*`` bindings): qkv [B, S, (H + 2*Hkv)*128], bidirectional and causal, S = 64 .. 1024.
 
 The reference is the float64 torch composition from the bf16 inputs (K/V expanded with repeat_interleave, so autograd
 sums each group's dk / dv; scale 1 / sqrt(128); the kernels' own dropout mask, keyed on the query head); the yardstick
@@ -135,7 +135,8 @@ def test_equals_d128_on_expanded_kv(causal):
 
 @needs_gpu
 def test_g1_is_bitwise_d128():
-    """kv_heads == heads: the d128 layout, and the d128 kernels' results bit for bit (S = 192, causal, p = 0.1)."""
+    """kv_heads == heads: the d128 layout, and the attention_d128_* bindings' results bit for bit (S = 192, causal,
+    p = 0.1).  Both run the same kernels at G = 1, so this pins the bindings' plumbing (Hkv = H, no tables)."""
     qkv, gout = _inputs(192, 2, 2)
     out, lse = _hip().attention_d128_forward(qkv, 2, SCALE, SEED, 0.1, True)
     dqkv = _hip().attention_d128_backward(qkv, out, lse, gout, 2, SCALE, SEED, 0.1, True)

@@ -1,5 +1,5 @@
 """GPU tests of rotary position embeddings at head dim 128: csrc/kernels/attention_rope.hip and the ROPE epilogues of
-attention_gqa.hip.  B = 2, inputs 1.5 x randn in bf16, base 10000, the tables of ops.attention.rope_tables; block
+attention_d128.hip.  B = 2, inputs 1.5 x randn in bf16, base 10000, the tables of ops.attention.rope_tables; block
 errors and their yardstick (the same composition in bf16) as in test_gpu_attention_gqa.py."""
 import functools
 

@@ -17,16 +17,15 @@ alternating the same way: the causal call in its heaviest-first workgroup order 
 bidirectional call at the same shape twice (S <= 512) and the SDPA ``is_causal=True`` path with BertLayer's permutes
 and copies.
 
-With ``--head-dim 128`` it times the head dim 128 kernels (attention_d128.hip), forward and backward separately,
-bidirectional or (``--causal``) causal, twice per round, against the SDPA path at the same head dim with the permutes,
-copy and concatenation.
+With ``--head-dim 128`` it times the head dim 128 kernels (attention_d128.hip) on multi-head attention, forward and
+backward separately, bidirectional or (``--causal``) causal, twice per round, against the SDPA path at the same head dim
+with the permutes, copy and concatenation.
 
-With ``--head-dim 128 --kv-heads N`` it times the grouped-query kernels (attention_gqa.hip) against the two ways to
-serve the call without them: K/V expanded for the head dim 128 kernels plus the group sum of dk / dv, and the SDPA
-fallback.
+With ``--head-dim 128 --kv-heads N`` it times the same kernels on grouped-query heads against the two ways to serve
+the call without grouping: K/V expanded to every query head plus the group sum of dk / dv, and the SDPA fallback.
 
 With ``--head-dim 128 --rope BASE`` (with or without ``--kv-heads``) it times ``self_attention(..., rope=BASE)``:
-the fused rotation (attention_rope.hip and the grouped-query backward's epilogues) against the rotation in torch
+the fused rotation (attention_rope.hip and the head dim 128 backward's epilogues) against the rotation in torch
 around the fused kernels and around SDPA, and the rotation kernel alone.
 
     python tools/bench_attention.py [calls] [--batch 128] [--seq 128] [--heads 12] [--lengths 0.5|random] [--causal]
@@ -170,7 +169,7 @@ def causal(args, H, qkv, dout, scale):
 
 
 def d128(args, H, qkv, dout):
-    """Head dim 128: forward and backward time of the attention_d128.hip kernels (timed twice per round: ``d128
+    """Head dim 128, multi-head: forward and backward time of the attention_d128.hip kernels (timed twice per round: ``d128
     again`` / ``d128`` is the run-to-run spread) and of the SDPA path with the permutes, the transposed output copy
     and the dq/dk/dv concatenation, the variants alternating over the rounds; bidirectional, or causal with --causal."""
     B, S, NH, c = args.batch, args.seq, args.heads, args.causal
@@ -204,9 +203,9 @@ def d128(args, H, qkv, dout):
 
 
 def gqa(args, H):
-    """Grouped-query heads at head dim 128 (``--kv-heads``): forward and backward time of the attention_gqa.hip
+    """Grouped-query heads at head dim 128 (``--kv-heads``): forward and backward time of the attention_d128.hip
     kernels (twice per round: ``gqa again`` / ``gqa`` is the run-to-run spread) against what serves the same call
-    without them: ``expand`` (repeat_interleave of K/V into [B, S, 3*H*128], the attention_d128.hip kernels on it, the
+    without grouping: ``expand`` (repeat_interleave of K/V into [B, S, 3*H*128], the same kernels at G = 1 on it, the
     torch group sum of the bf16 dk / dv slices and the concatenation into the grouped layout) and ``sdpa``
     (self_attention's fallback with ``_GQA_ENABLED = False``).  The variants alternate over the rounds."""
     B, S, NH, NKV, c = args.batch, args.seq, args.heads, args.kv_heads, args.causal
@@ -268,15 +267,14 @@ def gqa(args, H):
 def rope(args, H):
     """Rotary position embeddings at head dim 128 (``--rope BASE``, with or without ``--kv-heads``): forward and
     backward time of ``self_attention(..., rope=BASE)`` on its three routes, the variants alternating over the rounds:
-    ``rope`` (attention_rope.hip, the grouped-query forward on its result, the backward with the rotation in its
+    ``rope`` (attention_rope.hip, the head dim 128 forward on its result, the backward with the rotation in its
     epilogues; twice per round: ``rope again`` / ``rope`` is the run-to-run spread), ``torch+fused`` (``_ROPE_ENABLED =
     False``: Q and K rotated in torch around the fused kernels, autograd rotating dqkv back) and ``torch+sdpa`` (the
     fused attention switched off as well).  Then the rotation kernel alone with its bytes/s against a 5.3 TB/s
-    streaming roofline, and with ``kv_heads == heads`` the grouped-query kernels at G = 1 against attention_d128.hip's,
-    both without rotation."""
+    streaming roofline."""
     B, S, NH, c, base = args.batch, args.seq, args.heads, args.causal, args.rope
     NKV = NH if args.kv_heads is None else args.kv_heads
-    G, scale, kv = NH // NKV, 128 ** -0.5, args.kv_heads
+    G, kv = NH // NKV, args.kv_heads
     torch.manual_seed(0)
     qkv = (torch.randn(B, S, (NH + 2 * NKV) * 128, device="cuda") * 0.5).bfloat16()
     dout = (torch.randn(B, S, NH * 128, device="cuda") * 0.1).bfloat16()
@@ -306,12 +304,6 @@ def rope(args, H):
                               lambda y=y, q=q: torch.autograd.grad(y, q, dout, retain_graph=True))
         variants = {"rope": variants["rope"], "rope again": variants["rope"], "torch+fused": variants["torch+fused"],
                     "torch+sdpa": variants["torch+sdpa"]}
-        if G == 1:
-            out, lse = H.attention_d128_forward(qkv, NH, scale, 1234, p, c)
-            variants["plain d128"] = (lambda: H.attention_d128_forward(qkv, NH, scale, 1234, p, c),
-                                      lambda: H.attention_d128_backward(qkv, out, lse, dout, NH, scale, 1234, p, c))
-            variants["plain gqa"] = (lambda: H.attention_gqa_forward(qkv, NH, NH, scale, 1234, p, c),
-                                     lambda: H.attention_gqa_backward(qkv, out, lse, dout, NH, NH, scale, 1234, p, c))
         ts = {k: [] for k in variants}
         for _ in range(args.rounds):
             for k, (f, b) in variants.items():
@@ -322,11 +314,8 @@ def rope(args, H):
             m[k] = tot[len(tot) // 2]
             print("%s p=%.1f  %-11s fwd %7.1f us  bwd %7.1f us  fwd+bwd %7.1f us (min %7.1f max %7.1f) over %d rounds" % (
                 tag, p, k, fs[len(fs) // 2], bs[len(bs) // 2], m[k], tot[0], tot[-1], len(v)), flush=True)
-        line = "%s p=%.1f  fwd+bwd: rope / torch+fused %.3f   rope / torch+sdpa %.3f   rope again / rope %.3f" % (
-            tag, p, m["rope"] / m["torch+fused"], m["rope"] / m["torch+sdpa"], m["rope again"] / m["rope"])
-        if G == 1:
-            line += "   plain gqa / plain d128 %.3f" % (m["plain gqa"] / m["plain d128"])
-        print(line, flush=True)
+        print("%s p=%.1f  fwd+bwd: rope / torch+fused %.3f   rope / torch+sdpa %.3f   rope again / rope %.3f" % (
+            tag, p, m["rope"] / m["torch+fused"], m["rope"] / m["torch+sdpa"], m["rope again"] / m["rope"]), flush=True)
     rs = sorted(med(lambda: H.rope_forward(qkv, NH, NKV, cos, sin), args.calls) for _ in range(args.rounds))
     t, nbytes = rs[len(rs) // 2], 2 * qkv.numel() * 2 + 2 * cos.numel() * 4  # qkv read and written once, the tables once
     print("%s rope_forward alone %7.1f us (min %7.1f max %7.1f): %.2f TB/s of %d bytes, %.0f %% of 5.3 TB/s" % (
@@ -346,8 +335,8 @@ def main():
     ap.add_argument("--head-dim", type=int, choices=(64, 128), default=64,
                     help="128: the attention_d128.hip kernels against SDPA (with --causal: the causal ones)")
     ap.add_argument("--kv-heads", type=int, default=None,
-                    help="grouped-query heads (needs --head-dim 128): the attention_gqa.hip kernels against the "
-                         "expanded-K/V attention_d128.hip path and SDPA")
+                    help="grouped-query heads (needs --head-dim 128): the attention_d128.hip kernels on them against "
+                         "the expanded-K/V path and SDPA")
     ap.add_argument("--rope", type=float, default=None, metavar="BASE",
                     help="rotary position embeddings of this base (needs --head-dim 128, with or without --kv-heads): "
                          "the fused rotation against the rotation in torch around the fused kernels and around SDPA")
