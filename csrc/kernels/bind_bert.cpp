@@ -368,6 +368,97 @@ std::vector<at::Tensor> layernorm_backward(at::Tensor dy, at::Tensor s, at::Tens
     return {ds, dgamma, dbeta, dr};
 }
 
+// A contiguous bf16 GPU tensor of rows of rmsnorm.hip's lengths: {rows, D}
+std::pair<int64_t, int> check_rms_rows(const at::Tensor &t, const char *op, const char *name) {
+    check_dense(t, op, name, kAnyGpu, at::kBFloat16, t.numel());
+    TORCH_CHECK(t.dim() >= 1 && t.numel() > 0, op, ": ", name, " must have at least one row");
+    const int D = narrow(t.size(-1), op, "the row length");
+    TORCH_CHECK(kfk::rmsnorm_supported(D), op, ": ", name, " has an unsupported row length ", D,
+                " (a multiple of 256 from 256 to 8192)");
+    return {t.numel() / D, D};
+}
+
+// an optional bf16 operand of `like`'s shape on its device (null when absent)
+const uint16_t *check_rms_like(const OptTensor &t, const at::Tensor &like, const char *op, const char *name) {
+    if (!has(t)) return nullptr;
+    check_dense(*t, op, name, like.device(), at::kBFloat16, like.numel());
+    TORCH_CHECK(t->sizes() == like.sizes(), op, ": ", name, " must have the shape ", like.sizes(), ", got ", t->sizes());
+    return bf16(*t);
+}
+
+// y, s, rstd = rmsnorm(x [+ r]) over the last dim (rmsnorm.hip: bf16 rows, f32 gamma); s is x itself without r
+std::tuple<at::Tensor, at::Tensor, at::Tensor> rmsnorm_forward(at::Tensor x, OptTensor r, at::Tensor gamma, double eps) {
+    const char *op = "rmsnorm_forward";
+    const auto [rows, D] = check_rms_rows(x, op, "x");
+    const Dev dev = x.device();
+    const uint16_t *rp = check_rms_like(r, x, op, "r");
+    check_dense(gamma, op, "gamma", dev, at::kFloat, D);
+    c10::DeviceGuard gd(x.device());
+    auto y = at::empty_like(x);
+    auto sv = rp ? at::empty_like(x) : x;
+    auto rstd = at::empty({rows}, x.options().dtype(at::kFloat));
+    kfk::launch_rmsnorm_forward(bf16(x), rp, gamma.data_ptr<float>(), bf16_mut(y), rp ? bf16_mut(sv) : nullptr,
+                                rstd.data_ptr<float>(), rows, D, static_cast<float>(eps), stream_of(x, 0));
+    return {y, sv, rstd};
+}
+
+// (ds, dgamma): ds_in (optional) is the gradient that reaches s from the skip path, added ahead of the one rounding
+std::tuple<at::Tensor, at::Tensor> rmsnorm_backward(at::Tensor dy, OptTensor ds_in, at::Tensor s, at::Tensor gamma,
+                                                    at::Tensor rstd) {
+    const char *op = "rmsnorm_backward";
+    const auto [rows, D] = check_rms_rows(dy, op, "dy");
+    const Dev dev = dy.device();
+    const uint16_t *dp = check_rms_like(ds_in, dy, op, "ds_in");
+    const uint16_t *sp = check_rms_like(s, dy, op, "s");
+    check_dense(gamma, op, "gamma", dev, at::kFloat, D);
+    check_dense(rstd, op, "rstd", dev, at::kFloat, rows);
+    c10::DeviceGuard gd(dy.device());
+    auto ds = at::empty_like(dy);
+    auto partial = at::empty({kfk::rmsnorm_bwd_blocks(rows, D), D}, dy.options().dtype(at::kFloat));
+    auto dgamma = at::empty({D}, dy.options().dtype(at::kFloat));
+    kfk::launch_rmsnorm_backward(bf16(dy), dp, sp, gamma.data_ptr<float>(), rstd.data_ptr<float>(), bf16_mut(ds),
+                                 partial.data_ptr<float>(), dgamma.data_ptr<float>(), rows, D, stream_of(dy, 0));
+    return {ds, dgamma};
+}
+
+// gu [..., 2F] bf16 contiguous with F % 8 == 0: {rows, F}
+std::pair<int64_t, int64_t> check_gu(const at::Tensor &gu, const char *op) {
+    check_dense(gu, op, "gu", kAnyGpu, at::kBFloat16, gu.numel());
+    TORCH_CHECK(gu.dim() >= 1 && gu.size(-1) > 0 && gu.size(-1) % 16 == 0, op,
+                ": gu must be [..., 2F] with F a positive multiple of 8");
+    const int64_t F = gu.size(-1) / 2;
+    narrow(F / 8, op, "F / 8");
+    return {gu.numel() / (2 * F), F};
+}
+
+std::vector<int64_t> with_last(const at::Tensor &t, int64_t last) {
+    auto sz = t.sizes().vec();
+    sz.back() = last;
+    return sz;
+}
+
+// h [..., F] = silu(gate) * up of gu [..., 2F] (swiglu.hip: gate in the first F columns, up in the last F)
+at::Tensor swiglu_forward(at::Tensor gu) {
+    const auto [rows, F] = check_gu(gu, "swiglu_forward");
+    c10::DeviceGuard gd(gu.device());
+    auto h = at::empty(with_last(gu, F), gu.options());
+    kfk::launch_swiglu_forward(bf16(gu), bf16_mut(h), rows, F, stream_of(gu, 0));
+    return h;
+}
+
+// dgu [..., 2F] = (dgate, dup) in gu's layout, sigmoid recomputed from gu
+at::Tensor swiglu_backward(at::Tensor dh, at::Tensor gu) {
+    const char *op = "swiglu_backward";
+    const auto [rows, F] = check_gu(gu, op);
+    check_dense(dh, op, "dh", gu.device(), at::kBFloat16, rows * F);
+    TORCH_CHECK(dh.sizes() == at::IntArrayRef(with_last(gu, F)), op, ": dh must have gu's shape with F columns, got ",
+                dh.sizes());
+    c10::DeviceGuard gd(gu.device());
+    auto dgu = at::empty_like(gu);
+    kfk::launch_swiglu_backward(bf16(dh), bf16(gu), bf16_mut(dgu), rows, F, stream_of(gu, 0));
+    return dgu;
+}
+
 // The operands of gemm.hip's a[M, K] . b[N, K]^T (+ bias): returns {M, N, K} and the bias pointer (or null).
 struct NT {
     int64_t M, N, K;
@@ -458,6 +549,17 @@ void bind_bert(py::module_ &m) {
           "LayerNorm backward -> (ds, dgamma, dbeta, dr or None[, residual-input bias gradient])", py::arg("dy"),
           py::arg("s"), py::arg("gamma"), py::arg("mean"), py::arg("rstd"), py::arg("p") = 0.0, py::arg("seed") = 0,
           py::arg("rbias_dtype") = py::none());
+    m.def("rmsnorm_supported", &kfk::rmsnorm_supported);
+    m.def("rmsnorm_forward", &rmsnorm_forward,
+          "fused residual-add + RMSNorm (bf16 rows, D % 256 == 0 up to 8192) -> (y, s, rstd); s is x without r",
+          py::arg("x"), py::arg("r"), py::arg("gamma"), py::arg("eps"));
+    m.def("rmsnorm_backward", &rmsnorm_backward,
+          "RMSNorm backward -> (ds, dgamma); ds_in: the skip path's gradient of s, added before the rounding",
+          py::arg("dy"), py::arg("ds_in"), py::arg("s"), py::arg("gamma"), py::arg("rstd"));
+    m.def("swiglu_forward", &swiglu_forward, "h [..., F] = silu(gate) * up of gu [..., 2F] (gate first, F % 8 == 0)",
+          py::arg("gu"));
+    m.def("swiglu_backward", &swiglu_backward, "dgu [..., 2F] = (dgate, dup) from dh [..., F] and gu, in gu's layout",
+          py::arg("dh"), py::arg("gu"));
     m.def("attention_supported", &kfk::attention_supported);
     m.def("attention_causal_supported", &kfk::attention_causal_supported);
     m.def("attention_forward", &attention_forward,

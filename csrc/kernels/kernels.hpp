@@ -548,4 +548,22 @@ void launch_attention_gqa_backward(const uint16_t *qkv, const uint16_t *out, con
 void launch_rope_forward(const uint16_t *qkv, uint16_t *out, const float *cos, const float *sin, int B, int S, int H,
                          int Hkv, hipStream_t s);
 
+// Fused residual-add + RMSNorm over rows of D (rmsnorm.hip; D % 256 == 0, 256 .. 8192): bf16 x, r (optional), y, s
+// (= bf16(x + r), written only with r), f32 gamma and rstd (= rsqrt(mean(s^2) + eps) of the stored s).  Backward:
+// ds = bf16(ds_in (optional, the skip path's gradient of s) + rstd * g - s * c) and dgamma (f32) through
+// [rmsnorm_bwd_blocks(rows, D)][D] f32 partials.
+bool rmsnorm_supported(int D);
+int rmsnorm_bwd_blocks(int64_t rows, int D);
+void launch_rmsnorm_forward(const uint16_t *x, const uint16_t *r, const float *gamma, uint16_t *y, uint16_t *s,
+                            float *rstd, int64_t rows, int D, float eps, hipStream_t st);
+void launch_rmsnorm_backward(const uint16_t *dy, const uint16_t *ds_in, const uint16_t *s, const float *gamma,
+                             const float *rstd, uint16_t *ds, float *partial, float *dgamma, int64_t rows, int D,
+                             hipStream_t st);
+
+// SwiGLU (swiglu.hip) on gu [rows, 2F] bf16 (F % 8 == 0), gate in columns 0 .. F-1 and up in F .. 2F-1:
+// h [rows, F] = bf16(g * sigmoid(g) * u); backward dgu [rows, 2F] = (dg, du) in gu's layout, recomputed from gu.
+void launch_swiglu_forward(const uint16_t *gu, uint16_t *h, int64_t rows, int64_t F, hipStream_t st);
+void launch_swiglu_backward(const uint16_t *dh, const uint16_t *gu, uint16_t *dgu, int64_t rows, int64_t F,
+                            hipStream_t st);
+
 }  // namespace kfk

@@ -12,7 +12,7 @@ def get_model(name: str, **kw):
         "inception_v3": ("inception", "inception_v3"), "bert_base": ("bert", "bert_base"),
         "slp": ("slp", "SLP"), "gpt_base": ("gpt", "gpt_base"),
         "gpt_d128": ("gpt", "gpt_d128"), "gpt_gqa": ("gpt", "gpt_gqa"),
-        "gpt_rope": ("gpt", "gpt_rope"),
+        "gpt_rope": ("gpt", "gpt_rope"), "llama": ("llama", "llama"),
     }
     mod, fn = table[name]
     return getattr(importlib.import_module("kungfu_amd.models." + mod), fn)(**kw)
