@@ -2,13 +2,14 @@
 // kernels, bidirectional or causal (template parameter CAUSAL), S = 64 .. 1024 in steps of 64, bf16, dropout.  H query
 // heads share Hkv = H / G key/value heads, query head h reads K/V head h / G.  G is a run-time value: multi-head
 // attention (Hkv = H, G = 1), grouped-query attention and multi-query attention (Hkv = 1) are the same three kernels.
+// Causal with a sliding window (template parameter BAND; "Band" below): S = 64 .. 8192.
 //
 // Interface    qkv [B, S, (H + 2 Hkv) * 128], the output of one Linear(d, (H + 2 Hkv) * 128): a row holds the H query
 //              heads, then the Hkv key heads, then the Hkv value heads, 128 bf16 each.  Q of head h is at column
 //              h * 128, K at (H + h / G) * 128, V at (H + Hkv + h / G) * 128; row stride RS = (H + 2 Hkv) * 128.  At
 //              Hkv = H that is [B, S, 3, H, 128], what the attention_d128_* bindings pass.
 //              out [B, S, H, 128]; lse and dsum [B, H, S] f32 per query head; dqkv in qkv's layout, every element
-//              written once.  The keep_elem hash is on the global (query, key) index (q << 16 | k: S <= 1024 leaves
+//              written once.  The keep_elem hash is on the global (query, key) index (q << 16 | k: S <= 8192 leaves
 //              room), recomputed in the backward, and keyed on the query head: (seed, b * H + h, query, key).  No
 //              atomics, no zeroed scratch, no workgroup waits on another: bitwise reproducible.  No per-sequence
 //              lengths.  The argument block is attention_common.hpp's with H the query heads; Hkv is a kernel argument
@@ -65,6 +66,24 @@
 //              dK/dV: the diagonal block is the first step of every head's sub-stream, G times per workgroup: each
 //              head runs one masked step (dkv_step<true>) and then its loop of unmasked ones (dkv_step<false>), so the
 //              unmasked steps carry no mask code.
+// Band         BAND (causal only; w = window / 64 >= 1, a kernel argument of its own): query q sees keys q - 64 w < k <= q.
+//              Query block i needs key blocks max(0, i - w) .. i; key block j is needed by query blocks j ..
+//              min(n - 1, j + w).  Two blocks are masked, complementary triangles: the diagonal block (kk <= qq) and,
+//              for i >= w, the edge block i - w (kk > qq, MASK = EDGE); the blocks between carry no mask code.
+//              Forward and dQ stream in ascending order, the edge block first, the diagonal last: with w >= n there
+//              is no edge block and the steps, their order and their ring slots are the causal kernel's, so the
+//              results are its results bit for bit.  (The diagonal first and the edge last would never meet an empty
+//              row but would reorder those sums.)  The price is that the first step may see an empty row: qq = 63 has no
+//              key in its edge block and m_run is still -inf.  fwd_block<EDGE> takes that step's exponentials against 0
+//              where the maximum is -inf: alpha = e = 0, l_run and o stay 0 and m_run -inf, and the next step rescales
+//              by exp(-inf - m) = 0 as a first step does.  The diagonal block ends every stream and holds the row's
+//              own key, so l_run >= 1 at the division.  The ring slot follows the step, (kb - first) & 1, not the
+//              block.  The edge block has no pv_diagonal-style guard: its masked keys are past keys that other rows
+//              of the block read, their P is an exact 0, and V is assumed finite there, as the backward assumes
+//              everywhere.  dK/dV: each head's sub-stream is the diagonal step, unmasked steps, and the edge step
+//              kbk + w when kbk + w <= n - 1: G (min(n - 1, kbk + w) - kbk + 1) steps, the head boundary's prefetch
+//              going from a head's edge block to the next head's diagonal block.  The grid orders stay: all blocks
+//              with qb >= w (kbk <= n - 1 - w) weigh the same, so heaviest-first is harmless.
 //
 // Rows read or staged, by hand (n = S / 64; block b is rows 64 b .. 64 b + 63, inside [0, S) iff 0 <= b < n;
 // `last` = qb when causal, n - 1 when not; `first` = kbk when causal, 0 when not; hk = h / G < Hkv):
@@ -86,6 +105,21 @@
 //                                  workgroup, causal: block n - 1 only, no prefetch.
 //                   S = 64         n = 1, first = 0: G steps, block 0 of heads hk * G .. hk * G + G - 1; every
 //                                  prefetch is a head switch; G = 1: one step, no prefetch.
+//   band          forward, dQ: first block max(0, qb - w) >= 0, last block qb <= n - 1; the edge step (qb >= w) stages
+//                 qb - w + 1 <= qb since w >= 1; the dQ kernel's second pass starts over at the same first block.
+//                 dK/dV: a head's blocks are kbk .. last = min(n - 1, kbk + w) (GroupStream.n = last + 1); inside a
+//                 head the prefetch stages qb + 1 <= last, at a head boundary (head + 1, kbk), nothing behind the last
+//                 head's block `last`.
+//                   first workgroup  forward, dQ: qb = n - 1, blocks max(0, n - 1 - w) .. n - 1.  dK/dV: kbk = 0,
+//                                    blocks 0 .. min(n - 1, w) of each head.
+//                   last workgroup   forward, dQ: qb = 0, first = 0, block 0 only, no edge step (0 >= w is false).
+//                                    dK/dV: kbk = n - 1, kbk + w > n - 1: no edge step, block n - 1 of each head.
+//                   S = 64           n = 1: qb = kbk = 0, block 0 only, no edge step in any kernel.
+//                   w >= n           qb - w < 0 and kbk + w > n - 1 everywhere: no edge step, first = 0, last = n - 1,
+//                                    the causal rows above.
+//                   w = 1            forward, dQ, qb >= 1: the edge block qb - 1 (slot 0) and the diagonal qb (slot 1),
+//                                    the loop of unmasked steps is empty.  dK/dV, kbk <= n - 2: the diagonal step kbk
+//                                    and the edge step kbk + 1 per head, 2 G steps.
 //   columns       every staged or loaded row is 128 bf16 (256 bytes): Q, dq at h * 128 < H * 128; K, dk at
 //                 (H + hk) * 128 < (H + Hkv) * 128; V, dv at (H + Hkv + hk) * 128 < RS; dO, out at h * 128 of H * 128.
 //   dsum          the dQ kernel writes all 64 rows of its block and every (query head, block) has a workgroup: all
@@ -119,6 +153,10 @@ constexpr int KS = D2 / 32;     // MFMA K-steps over the head dim
 constexpr int FWD_LDS = 4 * IMG + BLK;      // ring 2 x (K, V); P
 constexpr int DQ_LDS = 4 * IMG + BLK;       // ring 2 x (K, V); dS
 constexpr int DKV_LDS = 6 * IMG + 2 * BLK;  // K, V; ring 2 x (Q, dO); P_drop; dS
+// The MASK of a block step, with qq / kk the query's and the key's row inside their 64-row blocks:
+constexpr int NOMASK = 0;  // every key visible
+constexpr int DIAG = 1;    // the diagonal block: visible iff kk <= qq
+constexpr int EDGE = 2;    // the band's edge block, w blocks before the query block: visible iff kk > qq
 
 // Stage NIMG images of 64 rows x 128 bf16 (256-byte rows) with 16-byte global_load_lds: image t row r comes from
 // src[t] + r * stride[t].  One load fills 1 KB = rows 4 pc .. 4 pc + 3, lane l the 16-byte piece l & 15 of row
@@ -211,10 +249,13 @@ __device__ __forceinline__ void pv_diagonal(const uint8_t *Vi, const uint8_t *Pi
 }
 
 // One step of the forward on the staged key block at key0 for this wave's 16 queries (Q pieces in qf, query `row`
-// in this lane, rows q0 .. of the block's P image): scores, online softmax, dropout, P V.  MASK (the diagonal
+// in this lane, rows q0 .. of the block's P image): scores, online softmax, dropout, P V.  DIAG (the diagonal
 // block) sets the scores of keys > row to -inf first; every row sees its own key there, and for query blocks > 0
 // the running max is already finite, so exp(-inf - m) = 0 exactly and no row is empty.
-template <bool MASK>
+// EDGE (the band's first step, m_run = -inf, l_run = 0, o = 0) sets the keys kk <= qq to -inf: the block's last row
+// sees none, its m stays -inf, and the exponentials are taken against 0 instead (header: Band), so alpha = e = 0 and
+// the row leaves the step as it entered it.  The plain MFMA follows: the masked P are exact zeros and V is finite.
+template <int MASK>
 __device__ __forceinline__ void fwd_block(const AttnArgs &a, uint32_t seed, int bh, const bf16x8 (&qf)[KS],
                                           const uint8_t *Ki, const uint8_t *Vi, uint8_t *Pi, int q0, int row, int key0,
                                           int lane, float &m_run, float &l_run, f32x4 (&o)[TD]) {
@@ -236,12 +277,15 @@ __device__ __forceinline__ void fwd_block(const AttnArgs &a, uint32_t seed, int 
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             acc[j][r] = scaled(acc[j][r], a.scale);
-            if constexpr (MASK) acc[j][r] = key0 + 16 * j + 4 * lg + r > row ? -INFINITY : acc[j][r];
+            if constexpr (MASK == DIAG) acc[j][r] = key0 + 16 * j + 4 * lg + r > row ? -INFINITY : acc[j][r];
+            if constexpr (MASK == EDGE) acc[j][r] = 16 * j + 4 * lg + r > q0 + lc ? acc[j][r] : -INFINITY;
             m = fmaxf(m, acc[j][r]);
         }
     m = fmaxf(m, __shfl_xor(m, 16));
     m = fmaxf(m, __shfl_xor(m, 32));
-    const float alpha = __expf(m_run - m);  // 0 at the first block (m_run = -inf, m finite)
+    float mref = m;  // what the exponentials are taken against: the maximum, but never -inf
+    if constexpr (MASK == EDGE) mref = m == -INFINITY ? 0.f : m;
+    const float alpha = __expf(m_run - mref);  // 0 at the first block (m_run = -inf, mref finite)
     float sum = 0.f;
 #pragma unroll
     for (int j = 0; j < TK; ++j) {
@@ -249,7 +293,7 @@ __device__ __forceinline__ void fwd_block(const AttnArgs &a, uint32_t seed, int 
         float p[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float e = __expf(acc[j][r] - m);
+            const float e = __expf(acc[j][r] - mref);
             sum += e;
             p[r] = keep_elem(seed, bh, row, key0 + kb0 + r, a.thresh) ? e * a.inv_keep : 0.f;
         }
@@ -265,7 +309,7 @@ __device__ __forceinline__ void fwd_block(const AttnArgs &a, uint32_t seed, int 
 #pragma unroll
         for (int r = 0; r < 4; ++r) o[c][r] *= alpha;
     lds_wave_sync();
-    if constexpr (MASK) {
+    if constexpr (MASK == DIAG) {
         pv_diagonal(Vi, Pi, q0, lane, o);
     } else {
 #pragma unroll
@@ -303,8 +347,9 @@ __device__ __forceinline__ void bwd_products(const bf16x8 (&qf)[KS], const bf16x
 }
 
 // This lane's share of D[q] = sum_key P_drop[q][key] dP[q][key] over the block (f32 throughout: the saved bf16 O
-// would put its rounding into dS = P o (dP - D)).  MASK: keys > row count as P = 0.
-template <bool MASK>
+// would put its rounding into dS = P o (dP - D)).  DIAG: keys > row count as P = 0; EDGE: keys kk <= qq do
+// (qq = row % 64: a query block starts at a multiple of 64).
+template <int MASK>
 __device__ __forceinline__ float bwd_dsum(const AttnArgs &a, uint32_t seed, int bh, const bf16x8 (&qf)[KS],
                                           const bf16x8 (&gf)[KS], const uint8_t *Ki, const uint8_t *Vi, int row,
                                           int key0, float l, int lane) {
@@ -318,14 +363,15 @@ __device__ __forceinline__ float bwd_dsum(const AttnArgs &a, uint32_t seed, int 
         for (int r = 0; r < 4; ++r) {
             const int key = key0 + 16 * j + 4 * lg + r;
             float p = __expf(scaled(sc[j][r], a.scale) - l);
-            if constexpr (MASK) p = key <= row ? p : 0.f;
+            if constexpr (MASK == DIAG) p = key <= row ? p : 0.f;
+            if constexpr (MASK == EDGE) p = key - key0 > (row & (BK - 1)) ? p : 0.f;
             if (keep_elem(seed, bh, row, key, a.thresh)) t += p * dp[j][r];
         }
     return t * a.inv_keep;
 }
 
 // P_drop and dS of the same 16 x 64 tile into row `lrow` of the 64 x 64 images Si (and Pi when not null).
-template <bool MASK>
+template <int MASK>
 __device__ __forceinline__ void bwd_scores(const AttnArgs &a, uint32_t seed, int bh, const bf16x8 (&qf)[KS],
                                            const bf16x8 (&gf)[KS], const uint8_t *Ki, const uint8_t *Vi, uint8_t *Pi,
                                            uint8_t *Si, int lrow, int row, int key0, float l, float dd, int lane) {
@@ -339,7 +385,8 @@ __device__ __forceinline__ void bwd_scores(const AttnArgs &a, uint32_t seed, int
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             float p = __expf(scaled(sc[j][r], a.scale) - l);
-            if constexpr (MASK) p = key0 + kb0 + r <= row ? p : 0.f;
+            if constexpr (MASK == DIAG) p = key0 + kb0 + r <= row ? p : 0.f;
+            if constexpr (MASK == EDGE) p = kb0 + r > (row & (BK - 1)) ? p : 0.f;
             const bool kp = keep_elem(seed, bh, row, key0 + kb0 + r, a.thresh);
             const float dpd = kp ? dp[j][r] * a.inv_keep : 0.f;
             pv[r] = kp ? p * a.inv_keep : 0.f;
@@ -372,8 +419,10 @@ __device__ __forceinline__ void gqa_block_of(int n, int G, int &bh, int &qb) {
 }
 
 // (two waves per SIMD: the register budget that lets two workgroups share a CU, as their 72 KB of LDS do)
-template <bool CAUSAL>
-KFK_NO_PK_F32 __global__ __launch_bounds__(256, 2) void attn_gqa_fwd_kernel(AttnArgs a, int Hkv, int S) {
+// w: the band's width in blocks (BAND only; header: Band)
+template <bool CAUSAL, bool BAND = false>
+KFK_NO_PK_F32 __global__ __launch_bounds__(256, 2) void attn_gqa_fwd_kernel(AttnArgs a, int Hkv, int S, int w) {
+    static_assert(CAUSAL || !BAND, "a band is causal");
     extern __shared__ __attribute__((aligned(1024))) uint8_t lds[];
     uint8_t *ring = lds, *Pi = lds + 4 * IMG;  // ring: 2 x (K block, V block)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -386,8 +435,10 @@ KFK_NO_PK_F32 __global__ __launch_bounds__(256, 2) void attn_gqa_fwd_kernel(Attn
     const uint16_t *seq = a.qkv + static_cast<int64_t>(b) * S * RS;
     const uint16_t *kbase = seq + D + hk * D2, *vbase = kbase + Hkv * D2;
     const int strd[2] = {RS, RS};
+    const int first = BAND ? max(0, qb - w) : 0;  // the first streamed key block; the edge block iff qb >= w
     {
-        const uint16_t *kv[2] = {kbase, vbase};
+        const int64_t r0 = static_cast<int64_t>(first) * BK * RS;
+        const uint16_t *kv[2] = {kbase + r0, vbase + r0};
         stage_rows256<2>(ring, kv, strd, wave, lane);
     }
     const int lg = lane >> 4, lc = lane & 15;
@@ -399,24 +450,36 @@ KFK_NO_PK_F32 __global__ __launch_bounds__(256, 2) void attn_gqa_fwd_kernel(Attn
     f32x4 o[TD];  // O^T[d][q]: lane -> d = 16 c + 4 lg + r of query lc
 #pragma unroll
     for (int c = 0; c < TD; ++c) o[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int nkb = CAUSAL ? qb + 1 : n;     // streamed key blocks 0 .. nkb - 1
-    const int nfull = CAUSAL ? qb : n;       // of which unmasked
-    for (int kb = 0; kb < nfull; ++kb) {
+    const int nkb = CAUSAL ? qb + 1 : n;     // streamed key blocks first .. nkb - 1
+    const int nfull = CAUSAL ? qb : n;       // of which not the diagonal
+    int kb = first;  // block kb is step kb - first of the stream, in ring slot (kb - first) & 1
+    if constexpr (BAND) {
+        if (qb >= w) {  // the edge block qb - w, the first step (slot 0), outside the loop; block first + 1 <= qb is next
+            wait_vmcnt<0>();
+            __syncthreads();
+            const int64_t r0 = static_cast<int64_t>(kb + 1) * BK * RS;
+            const uint16_t *kv[2] = {kbase + r0, vbase + r0};
+            stage_rows256<2>(ring + 2 * IMG, kv, strd, wave, lane);
+            fwd_block<EDGE>(a, seed, bh, qf, ring, ring + IMG, Pi, q0, row, kb * BK, lane, m_run, l_run, o);
+            ++kb;
+        }
+    }
+    for (; kb < nfull; ++kb) {
         wait_vmcnt<0>();
         __syncthreads();
-        const uint8_t *Ki = ring + (kb & 1) * 2 * IMG, *Vi = Ki + IMG;
+        const uint8_t *Ki = ring + ((kb - first) & 1) * 2 * IMG, *Vi = Ki + IMG;
         if (kb + 1 < nkb) {
             const int64_t r0 = static_cast<int64_t>(kb + 1) * BK * RS;
             const uint16_t *kv[2] = {kbase + r0, vbase + r0};
-            stage_rows256<2>(ring + ((kb + 1) & 1) * 2 * IMG, kv, strd, wave, lane);
+            stage_rows256<2>(ring + ((kb + 1 - first) & 1) * 2 * IMG, kv, strd, wave, lane);
         }
-        fwd_block<false>(a, seed, bh, qf, Ki, Vi, Pi, q0, row, kb * BK, lane, m_run, l_run, o);
+        fwd_block<NOMASK>(a, seed, bh, qf, Ki, Vi, Pi, q0, row, kb * BK, lane, m_run, l_run, o);
     }
     if constexpr (CAUSAL) {  // the diagonal block qb, last: nothing left to prefetch
         wait_vmcnt<0>();
         __syncthreads();
-        const uint8_t *Ki = ring + (qb & 1) * 2 * IMG, *Vi = Ki + IMG;
-        fwd_block<true>(a, seed, bh, qf, Ki, Vi, Pi, q0, row, qb * BK, lane, m_run, l_run, o);
+        const uint8_t *Ki = ring + ((qb - first) & 1) * 2 * IMG, *Vi = Ki + IMG;
+        fwd_block<DIAG>(a, seed, bh, qf, Ki, Vi, Pi, q0, row, qb * BK, lane, m_run, l_run, o);
     }
     const float inv = 1.f / l_run;  // l_run >= 1: the row's maximal key
     if (lg == 0) a.lse[static_cast<int64_t>(bh) * S + row] = m_run + __logf(l_run);
@@ -443,9 +506,11 @@ __device__ __forceinline__ void rope_transposed(const float *cos_t, const float 
     }
 }
 
-template <bool CAUSAL, bool ROPE>
+template <bool CAUSAL, bool ROPE, bool BAND = false>
 KFK_NO_PK_F32 __global__ __launch_bounds__(256) void attn_gqa_dq_kernel(AttnArgs a, float *dsum_g, int Hkv, int S,
-                                                                        const float *cos_t, const float *sin_t) {
+                                                                        const float *cos_t, const float *sin_t,
+                                                                        int w) {
+    static_assert(CAUSAL || !BAND, "a band is causal");
     extern __shared__ __attribute__((aligned(1024))) uint8_t lds[];
     uint8_t *ring = lds, *Si = lds + 4 * IMG;  // ring: 2 x (K, V)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -454,10 +519,12 @@ KFK_NO_PK_F32 __global__ __launch_bounds__(256) void attn_gqa_dq_kernel(AttnArgs
     gqa_block_of<CAUSAL>(n, G, bh, qb);
     const int b = bh / a.H, h = bh - b * a.H, hk = h / G;
     const int D = a.H * D2, RS = D + 2 * Hkv * D2;
-    const int nb = CAUSAL ? qb + 1 : n;  // streamed key blocks 0 .. nb - 1
+    const int first = BAND ? max(0, qb - w) : 0;        // the edge block iff qb >= w
+    const int nb = (CAUSAL ? qb + 1 : n) - first;       // streamed key blocks first .. first + nb - 1
     const uint32_t seed = call_seed(a);
     const uint16_t *seq = a.qkv + static_cast<int64_t>(b) * S * RS;
-    const uint16_t *kbase = seq + D + hk * D2, *vbase = kbase + Hkv * D2;
+    const uint16_t *kbase = seq + D + hk * D2 + static_cast<int64_t>(first) * BK * RS;  // row 0 of block `first`
+    const uint16_t *vbase = kbase + Hkv * D2;
     const uint16_t *dob = a.dout + static_cast<int64_t>(b) * S * D + h * D2;
     const int strd[2] = {RS, RS};
     {
@@ -476,22 +543,24 @@ KFK_NO_PK_F32 __global__ __launch_bounds__(256) void attn_gqa_dq_kernel(AttnArgs
 #pragma unroll
     for (int c = 0; c < TD; ++c) o[c] = f32x4{0.f, 0.f, 0.f, 0.f};
     // the K / V blocks stream past twice: steps 0 .. nb - 1 sum D, steps nb .. 2 nb - 1 form dS and dQ; causal: the
-    // last step of each pass is the diagonal block
+    // last step of each pass is the diagonal block; band: the first is the edge block where there is one
     for (int it = 0; it < 2 * nb; ++it) {
         wait_vmcnt<0>();
         __syncthreads();
-        const int kb = it < nb ? it : it - nb;
+        const int kb = first + (it < nb ? it : it - nb);
         const bool diag = CAUSAL && kb == qb;
+        const bool edge = BAND && kb + w == qb;
         const uint8_t *Ki = ring + (it & 1) * 2 * IMG, *Vi = Ki + IMG;
         if (it + 1 < 2 * nb) {
-            const int nx = it + 1 < nb ? it + 1 : it + 1 - nb;  // <= nb - 1
+            const int nx = it + 1 < nb ? it + 1 : it + 1 - nb;  // <= nb - 1: block first + nx <= qb (n - 1)
             const int64_t r0 = static_cast<int64_t>(nx) * BK * RS;
             const uint16_t *kv[2] = {kbase + r0, vbase + r0};
             stage_rows256<2>(ring + ((it + 1) & 1) * 2 * IMG, kv, strd, wave, lane);
         }
         if (it < nb) {
-            dd += diag ? bwd_dsum<true>(a, seed, bh, qf, gf, Ki, Vi, row, kb * BK, l, lane)
-                       : bwd_dsum<false>(a, seed, bh, qf, gf, Ki, Vi, row, kb * BK, l, lane);
+            dd += diag   ? bwd_dsum<DIAG>(a, seed, bh, qf, gf, Ki, Vi, row, kb * BK, l, lane)
+                  : edge ? bwd_dsum<EDGE>(a, seed, bh, qf, gf, Ki, Vi, row, kb * BK, l, lane)
+                         : bwd_dsum<NOMASK>(a, seed, bh, qf, gf, Ki, Vi, row, kb * BK, l, lane);
             if (it == nb - 1) {  // the query's four lanes (lg) hold 16 keys of every block each
                 dd += __shfl_xor(dd, 16);
                 dd += __shfl_xor(dd, 32);
@@ -499,8 +568,9 @@ KFK_NO_PK_F32 __global__ __launch_bounds__(256) void attn_gqa_dq_kernel(AttnArgs
             }
             continue;
         }
-        if (diag) bwd_scores<true>(a, seed, bh, qf, gf, Ki, Vi, nullptr, Si, qw0 + lc, row, kb * BK, l, dd, lane);
-        else bwd_scores<false>(a, seed, bh, qf, gf, Ki, Vi, nullptr, Si, qw0 + lc, row, kb * BK, l, dd, lane);
+        if (diag) bwd_scores<DIAG>(a, seed, bh, qf, gf, Ki, Vi, nullptr, Si, qw0 + lc, row, kb * BK, l, dd, lane);
+        else if (edge) bwd_scores<EDGE>(a, seed, bh, qf, gf, Ki, Vi, nullptr, Si, qw0 + lc, row, kb * BK, l, dd, lane);
+        else bwd_scores<NOMASK>(a, seed, bh, qf, gf, Ki, Vi, nullptr, Si, qw0 + lc, row, kb * BK, l, dd, lane);
         lds_wave_sync();
         // dQ^T[d][q] += sum_key K[key][d] dS[q][key]
 #pragma unroll
@@ -528,14 +598,15 @@ KFK_NO_PK_F32 __global__ __launch_bounds__(256) void attn_gqa_dq_kernel(AttnArgs
 // What a dK/dV workgroup streams: the sequence's qkv and dO rows (column 0) and their strides, the blocks per head
 struct GroupStream {
     const uint16_t *seq, *dseq;  // qkv [S, RS], dout [S, D] of the sequence
-    int RS, D, S, n, first;      // a head's sub-stream is blocks first .. n - 1
+    int RS, D, S, n, first;      // a head's sub-stream is blocks first .. n - 1 (band: n - 1 is min(S / 64 - 1, first + w))
     int hlast;                   // the group's last query head
 };
 
 // One dK/dV step on the staged block qb of query head h (ring slot `slot`), after starting the DMA of the stream's next
 // step into the other slot: block qb + 1 of h, or block `first` of head h + 1 behind h's last block; nothing behind
-// the last head's last block.  MASK: the diagonal block (keys beyond a query give P = dS = 0), chosen outside.
-template <bool MASK>
+// the last head's last block.  MASK: the diagonal block (keys beyond a query give P = dS = 0) or the band's edge block
+// (keys kk <= qq do), chosen outside.
+template <int MASK>
 __device__ __forceinline__ void dkv_step(const AttnArgs &a, const float *dsum_g, uint32_t seed, const GroupStream &g,
                                          int b, int h, int qb, int kbk, int slot, uint8_t *lds, int wave, int lane,
                                          f32x4 (&dv)[TD], f32x4 (&dk)[TD]) {
@@ -579,10 +650,11 @@ __device__ __forceinline__ void dkv_step(const AttnArgs &a, const float *dsum_g,
     }
 }
 
-template <bool CAUSAL, bool ROPE>
+template <bool CAUSAL, bool ROPE, bool BAND = false>
 KFK_NO_PK_F32 __global__ __launch_bounds__(256) void attn_gqa_dkv_kernel(AttnArgs a, const float *dsum_g, int Hkv,
                                                                          int S, const float *cos_t,
-                                                                         const float *sin_t) {
+                                                                         const float *sin_t, int w) {
+    static_assert(CAUSAL || !BAND, "a band is causal");
     extern __shared__ __attribute__((aligned(1024))) uint8_t lds[];  // K, V resident; ring 2 x (Q, dO); P_drop; dS
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nbs = S / BK, G = a.H / Hkv;
@@ -593,7 +665,9 @@ KFK_NO_PK_F32 __global__ __launch_bounds__(256) void attn_gqa_dkv_kernel(AttnArg
     const uint32_t seed = call_seed(a);
     GroupStream g;
     g.seq = a.qkv + static_cast<int64_t>(b) * S * RS, g.dseq = a.dout + static_cast<int64_t>(b) * S * D;
-    g.RS = RS, g.D = D, g.S = S, g.n = nbs, g.first = CAUSAL ? kbk : 0, g.hlast = h0 + G - 1;
+    // band: query blocks beyond kbk + w see nothing of this key block, and block kbk + w is the edge block
+    const bool has_edge = BAND && kbk + w < nbs;
+    g.RS = RS, g.D = D, g.S = S, g.n = has_edge ? kbk + w + 1 : nbs, g.first = CAUSAL ? kbk : 0, g.hlast = h0 + G - 1;
     const int kcol = D + hk * D2, vcol = kcol + Hkv * D2;  // the K/V head's columns of a qkv (and dqkv) row
     {
         const uint16_t *krow = g.seq + static_cast<int64_t>(kbk) * BK * RS;
@@ -614,11 +688,15 @@ KFK_NO_PK_F32 __global__ __launch_bounds__(256) void attn_gqa_dkv_kernel(AttnArg
     for (int h = h0; h <= g.hlast; ++h) {
         int qb = g.first;
         if constexpr (CAUSAL) {  // the diagonal block opens every head's sub-stream
-            dkv_step<true>(a, dsum_g, seed, g, b, h, qb, kbk, slot, lds, wave, lane, dv, dk);
+            dkv_step<DIAG>(a, dsum_g, seed, g, b, h, qb, kbk, slot, lds, wave, lane, dv, dk);
             ++qb, slot ^= 1;
         }
-        for (; qb < nbs; ++qb, slot ^= 1)
-            dkv_step<false>(a, dsum_g, seed, g, b, h, qb, kbk, slot, lds, wave, lane, dv, dk);
+        for (; qb < g.n - has_edge; ++qb, slot ^= 1)
+            dkv_step<NOMASK>(a, dsum_g, seed, g, b, h, qb, kbk, slot, lds, wave, lane, dv, dk);
+        if (has_edge) {  // and the edge block kbk + w >= kbk + 1 closes it
+            dkv_step<EDGE>(a, dsum_g, seed, g, b, h, qb, kbk, slot, lds, wave, lane, dv, dk);
+            slot ^= 1;
+        }
     }
     if constexpr (ROPE) {  // the position is the key row
 #pragma unroll
@@ -636,58 +714,69 @@ KFK_NO_PK_F32 __global__ __launch_bounds__(256) void attn_gqa_dkv_kernel(AttnArg
     }
 }
 
-void check(int S, int H, int Hkv) {
-    if (!attention_gqa_supported(S, H, Hkv))
-        throw std::invalid_argument("attention: head dim 128 needs S % 64 == 0, 64 <= S <= 1024, "
-                                    "1 <= kv_heads <= heads and heads % kv_heads == 0");
+// -> the band's width in blocks (0: no window)
+int check(int B, int S, int H, int Hkv, bool causal, int window) {
+    if (!attention_gqa_supported(S, H, Hkv, window))
+        throw std::invalid_argument("attention: head dim 128 needs S % 64 == 0, 64 <= S <= 1024 (8192 with a window, "
+                                    "a positive multiple of 64), 1 <= kv_heads <= heads and heads % kv_heads == 0");
+    if (window && !causal) throw std::invalid_argument("attention: a window needs causal attention");
+    if (static_cast<int64_t>(B) * H * (S / BK) > INT32_MAX)
+        throw std::invalid_argument("attention: B * heads * S / 64 workgroups do not fit one grid");
+    return window / BK;
 }
 
-template <bool CAUSAL>
-void forward(const AttnArgs &a, int Hkv, int grid, int S, hipStream_t s) {
-    static const bool attr = (raise_lds(attn_gqa_fwd_kernel<CAUSAL>, FWD_LDS), true);
+template <bool CAUSAL, bool BAND = false>
+void forward(const AttnArgs &a, int Hkv, int grid, int S, hipStream_t s, int w = 0) {
+    static const bool attr = (raise_lds(attn_gqa_fwd_kernel<CAUSAL, BAND>, FWD_LDS), true);
     (void)attr;
-    attn_gqa_fwd_kernel<CAUSAL><<<grid, 256, FWD_LDS, s>>>(a, Hkv, S);
+    attn_gqa_fwd_kernel<CAUSAL, BAND><<<grid, 256, FWD_LDS, s>>>(a, Hkv, S, w);
 }
 
-template <bool CAUSAL, bool ROPE>
+template <bool CAUSAL, bool ROPE, bool BAND = false>
 void backward(const AttnArgs &a, float *dsum, int Hkv, int B, int S, const float *cos, const float *sin,
-              hipStream_t s) {
-    static const bool attr = (raise_lds(attn_gqa_dq_kernel<CAUSAL, ROPE>, DQ_LDS),
-                              raise_lds(attn_gqa_dkv_kernel<CAUSAL, ROPE>, DKV_LDS), true);
+              hipStream_t s, int w = 0) {
+    static const bool attr = (raise_lds(attn_gqa_dq_kernel<CAUSAL, ROPE, BAND>, DQ_LDS),
+                              raise_lds(attn_gqa_dkv_kernel<CAUSAL, ROPE, BAND>, DKV_LDS), true);
     (void)attr;
     const int n = S / BK;
     // the dQ kernel fills all [B, H, S] of dsum, the dK/dV kernel reads them (stream order)
-    attn_gqa_dq_kernel<CAUSAL, ROPE><<<B * a.H * n, 256, DQ_LDS, s>>>(a, dsum, Hkv, S, cos, sin);
-    attn_gqa_dkv_kernel<CAUSAL, ROPE><<<B * Hkv * n, 256, DKV_LDS, s>>>(a, dsum, Hkv, S, cos, sin);
+    attn_gqa_dq_kernel<CAUSAL, ROPE, BAND><<<B * a.H * n, 256, DQ_LDS, s>>>(a, dsum, Hkv, S, cos, sin, w);
+    attn_gqa_dkv_kernel<CAUSAL, ROPE, BAND><<<B * Hkv * n, 256, DKV_LDS, s>>>(a, dsum, Hkv, S, cos, sin, w);
 }
 
 }  // namespace
 
 bool attention_d128_supported(int S) { return S >= 64 && S <= 1024 && S % 64 == 0; }
 
-bool attention_gqa_supported(int S, int heads, int kv_heads) {
-    return attention_d128_supported(S) && kv_heads >= 1 && heads >= kv_heads && heads % kv_heads == 0;
+bool attention_gqa_supported(int S, int heads, int kv_heads, int window) {
+    const bool s_ok = window == 0 ? attention_d128_supported(S)
+                                  : window > 0 && window % 64 == 0 && S >= 64 && S <= kAttentionWindowMaxS && S % 64 == 0;
+    return s_ok && kv_heads >= 1 && heads >= kv_heads && heads % kv_heads == 0;
 }
 
 void launch_attention_gqa_forward(const uint16_t *qkv, uint16_t *out, float *lse, int B, int S, int H, int Hkv,
-                                  float scale, uint32_t seed, float p_drop, bool causal, hipStream_t s) {
-    check(S, H, Hkv);
+                                  float scale, uint32_t seed, float p_drop, bool causal, hipStream_t s, int window) {
+    const int w = check(B, S, H, Hkv, causal, window);
     const AttnArgs a = make_args(qkv, out, lse, nullptr, nullptr, H, scale, seed, p_drop);
     const int grid = B * H * (S / BK);
-    if (causal) forward<true>(a, Hkv, grid, S, s);
+    if (w) forward<true, true>(a, Hkv, grid, S, s, w);
+    else if (causal) forward<true>(a, Hkv, grid, S, s);
     else forward<false>(a, Hkv, grid, S, s);
 }
 
 void launch_attention_gqa_backward(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *dout,
                                    uint16_t *dqkv, float *dsum, int B, int S, int H, int Hkv, float scale,
                                    uint32_t seed, float p_drop, bool causal, hipStream_t s, const float *cos,
-                                   const float *sin) {
-    check(S, H, Hkv);
+                                   const float *sin, int window) {
+    const int w = check(B, S, H, Hkv, causal, window);
     if (!cos != !sin) throw std::invalid_argument("attention: the rotary tables cos and sin come together");
     if (!dsum) throw std::invalid_argument("attention: the head dim 128 backward needs the [B, H, S] f32 dsum buffer");
     const AttnArgs a = make_args(qkv, const_cast<uint16_t *>(out), const_cast<float *>(lse), dout, dqkv, H, scale, seed,
                                  p_drop);
-    if (cos) {
+    if (w) {
+        if (cos) backward<true, true, true>(a, dsum, Hkv, B, S, cos, sin, s, w);
+        else backward<true, false, true>(a, dsum, Hkv, B, S, nullptr, nullptr, s, w);
+    } else if (cos) {
         if (causal) backward<true, true>(a, dsum, Hkv, B, S, cos, sin, s);
         else backward<false, true>(a, dsum, Hkv, B, S, cos, sin, s);
     } else {

@@ -6,7 +6,8 @@
 // Convention   Half-split ("rotate_half": Hugging Face LLaMA, GPT-NeoX) over the whole head, positions 0 .. S - 1.
 //              With c = cos[t][i], s = sin[t][i] of position t, i = 0 .. 63:
 //                x'[i] = x[i] c - x[i + 64] s        x'[i + 64] = x[i + 64] c + x[i] s
-//              cos and sin are f32 [S, 64] tables made on the host (angles reach 1023 rad: no sine is evaluated here).
+//              cos and sin are f32 [S, 64] tables made on the host (angles reach 8191 rad: no sine is evaluated here).
+//              S = 64 .. 8192 in steps of 64: beyond 1024 for attention_d128.hip's band kernels.
 // Interface    qkv and the result [B, S, NH * 128] bf16 with NH = H + 2 Hkv: a row (token) holds the H query heads,
 //              the Hkv key heads, the Hkv value heads, 256 bytes each.  Heads 0 .. H + Hkv - 1 are rotated in f32 (one
 //              product and one fma per element) and rounded once (pack_bf16x2_hw); the value heads are copied bit for
@@ -110,8 +111,8 @@ KFK_NO_PK_F32 __global__ __launch_bounds__(256) void rope_fwd_kernel(const uint1
 
 void launch_rope_forward(const uint16_t *qkv, uint16_t *out, const float *cos, const float *sin, int B, int S, int H,
                          int Hkv, hipStream_t s) {
-    if (!attention_gqa_supported(S, H, Hkv))
-        throw std::invalid_argument("rope: needs S % 64 == 0, 64 <= S <= 1024, 1 <= kv_heads <= heads and "
+    if (!attention_gqa_supported(S, H, Hkv, 64))  // (any window: the S of the band kernels that read long results)
+        throw std::invalid_argument("rope: needs S % 64 == 0, 64 <= S <= 8192, 1 <= kv_heads <= heads and "
                                     "heads % kv_heads == 0");
     const int64_t tokens = static_cast<int64_t>(B) * S;  // a multiple of 64
     if (tokens / ROPE_TOKENS > INT32_MAX) throw std::invalid_argument("rope: too many tokens for one grid");

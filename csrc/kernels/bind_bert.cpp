@@ -188,22 +188,23 @@ std::tuple<int, int, int> check_qkv_d128(const at::Tensor &qkv, int64_t heads, c
 }
 
 // The head dim 128 kernels on a checked qkv [B, S, (H + 2*Hkv)*128] -> (out [B, S, H*128] bf16, lse [B, H, S] f32)
+// (window: the checked band width in keys, 0 without)
 std::vector<at::Tensor> d128_forward(const at::Tensor &qkv, int B, int S, int H, int Hkv, double scale, int64_t seed,
-                                     double p_drop, bool causal) {
+                                     double p_drop, bool causal, int window = 0) {
     c10::DeviceGuard gd(qkv.device());
     auto out = at::empty({B, S, H * 128}, qkv.options());
     auto lse = at::empty({B, H, S}, qkv.options().dtype(at::kFloat));
     kfk::launch_attention_gqa_forward(bf16(qkv), bf16_mut(out), lse.data_ptr<float>(), B, S, H, Hkv,
                                       static_cast<float>(scale), static_cast<uint32_t>(seed),
-                                      static_cast<float>(p_drop), causal, stream_of(qkv, 0));
+                                      static_cast<float>(p_drop), causal, stream_of(qkv, 0), window);
     return {out, lse};
 }
 
 // Their backward for the binding `op`: checks out, dout and lse against the checked qkv -> dqkv in qkv's layout
-// (cos, sin: the checked rotary tables, or both null)
+// (cos, sin: the checked rotary tables, or both null; window as the forward's)
 at::Tensor d128_backward(const char *op, const at::Tensor &qkv, const at::Tensor &out, const at::Tensor &lse,
                          at::Tensor dout, int B, int S, int H, int Hkv, double scale, int64_t seed, double p_drop,
-                         bool causal, const float *cos, const float *sin) {
+                         bool causal, const float *cos, const float *sin, int window = 0) {
     const Dev dev = qkv.device();
     check_dense(out, op, "out", dev, at::kBFloat16, out.numel());
     TORCH_CHECK(out.sizes() == at::IntArrayRef({B, S, H * 128}), op, ": out must be the forward's [B, S, H*128] output");
@@ -218,7 +219,7 @@ at::Tensor d128_backward(const char *op, const at::Tensor &qkv, const at::Tensor
     kfk::launch_attention_gqa_backward(bf16(qkv), bf16(out), lse.data_ptr<float>(), bf16(dout), bf16_mut(dqkv),
                                        dsum.data_ptr<float>(), B, S, H, Hkv, static_cast<float>(scale),
                                        static_cast<uint32_t>(seed), static_cast<float>(p_drop), causal,
-                                       stream_of(qkv, 0), cos, sin);
+                                       stream_of(qkv, 0), cos, sin, window);
     return dqkv;
 }
 
@@ -238,25 +239,40 @@ at::Tensor attention_d128_backward(at::Tensor qkv, at::Tensor out, at::Tensor ls
 }
 
 // Grouped-query heads at head dim 128 (attention_d128.hip): contiguous bf16 [B, S, (H + 2*Hkv)*128] with H % Hkv == 0
-// and S a multiple of 64 up to 1024: {B, S, H, Hkv}
-std::tuple<int, int, int, int> check_qkv_gqa(const at::Tensor &qkv, int64_t heads, int64_t kv_heads, const char *op) {
+// and S a multiple of 64 up to 1024: {B, S, H, Hkv}.  window > 0 (attention_gqa_*'s band, a checked multiple of 64;
+// rope_forward passes 64 for the same S): S up to 8192.
+std::tuple<int, int, int, int> check_qkv_gqa(const at::Tensor &qkv, int64_t heads, int64_t kv_heads, const char *op,
+                                             int window = 0) {
     TORCH_CHECK(kv_heads >= 1 && heads >= kv_heads && heads % kv_heads == 0, op,
                 ": kv_heads must be at least 1 and divide heads, got heads ", heads, ", kv_heads ", kv_heads);
     check_dense(qkv, op, "qkv", kAnyGpu, at::kBFloat16, qkv.numel());
     const int H = narrow(heads, op, "heads"), Hkv = narrow(kv_heads, op, "kv_heads");
-    TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == (heads + 2 * kv_heads) * 128 && qkv.size(1) <= 1024 &&
-                    kfk::attention_gqa_supported(static_cast<int>(qkv.size(1)), H, Hkv),
-                op, ": qkv must be [B, S, (H + 2*Hkv)*128] with S a multiple of 64 from 64 to 1024");
+    TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == (heads + 2 * kv_heads) * 128 &&
+                    qkv.size(1) <= kfk::kAttentionWindowMaxS &&
+                    kfk::attention_gqa_supported(static_cast<int>(qkv.size(1)), H, Hkv, window),
+                op, ": qkv must be [B, S, (H + 2*Hkv)*128] with S a multiple of 64 from 64 to 1024, or to 8192 with "
+                    "window (rope_forward: always)");
     check_extent32(op, "the workgroup count", {qkv.size(0), heads, qkv.size(1) / 64});
     return {narrow(qkv.size(0), op, "B"), narrow(qkv.size(1), op, "S"), H, Hkv};
 }
 
+// The window keyword of attention_gqa_*: 0 (none) or a positive multiple of 64 on a causal call -> as an int
+int check_window(int64_t window, bool causal, const char *op) {
+    TORCH_CHECK(window >= 0 && window % 64 == 0, op, ": window must be a positive multiple of 64 (0: no window), got ",
+                window);
+    TORCH_CHECK(window == 0 || causal, op, ": window must come with causal = true");
+    return narrow(window, op, "window");
+}
+
 // Fused grouped-query self-attention at head dim 128: qkv [B, S, (H + 2*Hkv)*128] bf16 contiguous (query heads, key
 // heads, value heads; query head h reads K/V head h / (H / Hkv)) -> (out [B, S, H*128] bf16, lse [B, H, S] f32)
+// window > 0: causal, query q sees keys q - window < k <= q, S up to 8192
 std::vector<at::Tensor> attention_gqa_forward(at::Tensor qkv, int64_t heads, int64_t kv_heads, double scale,
-                                              int64_t seed, double p_drop, bool causal) {
-    const auto [B, S, H, Hkv] = check_qkv_gqa(qkv, heads, kv_heads, "attention_gqa_forward");
-    return d128_forward(qkv, B, S, H, Hkv, scale, seed, p_drop, causal);
+                                              int64_t seed, double p_drop, bool causal, int64_t window) {
+    const char *op = "attention_gqa_forward";
+    const int win = check_window(window, causal, op);
+    const auto [B, S, H, Hkv] = check_qkv_gqa(qkv, heads, kv_heads, op, win);
+    return d128_forward(qkv, B, S, H, Hkv, scale, seed, p_drop, causal, win);
 }
 
 // A rotary table (attention_rope.hip): contiguous f32 [S, 64] on qkv's device
@@ -271,7 +287,7 @@ const float *check_rope_table(const at::Tensor &t, const at::Tensor &qkv, const 
 // the Q and K heads rotated (half-split convention, positions 0 .. S-1, f32, one rounding) and the V heads copied
 at::Tensor rope_forward(at::Tensor qkv, int64_t heads, int64_t kv_heads, at::Tensor cos, at::Tensor sin) {
     const char *op = "rope_forward";
-    const auto [B, S, H, Hkv] = check_qkv_gqa(qkv, heads, kv_heads, op);
+    const auto [B, S, H, Hkv] = check_qkv_gqa(qkv, heads, kv_heads, op, 64);  // rows are independent: the longest S
     const float *c = check_rope_table(cos, qkv, op, "cos"), *s = check_rope_table(sin, qkv, op, "sin");
     check_extent32(op, "the token count", {qkv.size(0), qkv.size(1)});
     c10::DeviceGuard gd(qkv.device());
@@ -285,13 +301,14 @@ at::Tensor rope_forward(at::Tensor qkv, int64_t heads, int64_t kv_heads, at::Ten
 // transposed rotation in the kernels' epilogues, f32, ahead of the one rounding)
 at::Tensor attention_gqa_backward(at::Tensor qkv, at::Tensor out, at::Tensor lse, at::Tensor dout, int64_t heads,
                                   int64_t kv_heads, double scale, int64_t seed, double p_drop, bool causal,
-                                  OptTensor cos, OptTensor sin) {
+                                  OptTensor cos, OptTensor sin, int64_t window) {
     const char *op = "attention_gqa_backward";
-    const auto [B, S, H, Hkv] = check_qkv_gqa(qkv, heads, kv_heads, op);
+    const int win = check_window(window, causal, op);
+    const auto [B, S, H, Hkv] = check_qkv_gqa(qkv, heads, kv_heads, op, win);
     TORCH_CHECK(has(cos) == has(sin), op, ": cos and sin must be given together, got only ", has(cos) ? "cos" : "sin");
     const float *ct = has(cos) ? check_rope_table(*cos, qkv, op, "cos") : nullptr;
     const float *st = has(sin) ? check_rope_table(*sin, qkv, op, "sin") : nullptr;
-    return d128_backward(op, qkv, out, lse, dout, B, S, H, Hkv, scale, seed, p_drop, causal, ct, st);
+    return d128_backward(op, qkv, out, lse, dout, B, S, H, Hkv, scale, seed, p_drop, causal, ct, st, win);
 }
 
 // y, s, mean, rstd = layernorm(x [+ r]) over the last dim (bf16 rows, f32 affine)
@@ -584,24 +601,25 @@ void bind_bert(py::module_ &m) {
           py::arg("out"), py::arg("lse"), py::arg("dout"), py::arg("heads"), py::arg("scale"), py::arg("seed"),
           py::arg("p_drop"), py::arg("causal") = false);
     m.def("attention_gqa_supported", &kfk::attention_gqa_supported, py::arg("S"), py::arg("heads"),
-          py::arg("kv_heads"));
+          py::arg("kv_heads"), py::arg("window") = 0);
     m.def("attention_gqa_forward", &attention_gqa_forward,
           "fused grouped-query self-attention forward at head dim 128: qkv [B, S, (heads + 2*kv_heads)*128] (query, "
           "key, value heads; query head h reads K/V head h / (heads / kv_heads)), S 64..1024 in steps of 64, dropout, "
-          "causal or not -> (out [B, S, heads*128], lse [B, heads, S])",
+          "causal or not -> (out [B, S, heads*128], lse [B, heads, S]); window (a positive multiple of 64, causal "
+          "only; 0: none): query q sees keys q - window < k <= q, S 64..8192",
           py::arg("qkv"), py::arg("heads"), py::arg("kv_heads"), py::arg("scale"), py::arg("seed"), py::arg("p_drop"),
-          py::arg("causal") = false);
+          py::arg("causal") = false, py::arg("window") = 0);
     m.def("attention_gqa_backward", &attention_gqa_backward,
           "fused grouped-query self-attention backward -> dqkv in qkv's layout (dk / dv summed over each group in f32)"
           "; cos, sin (f32 [S, 64], both or neither): qkv is rope_forward's result and dq / dk are rotated back in "
-          "the kernels' epilogues",
+          "the kernels' epilogues; window as the forward's",
           py::arg("qkv"), py::arg("out"), py::arg("lse"), py::arg("dout"), py::arg("heads"), py::arg("kv_heads"),
           py::arg("scale"), py::arg("seed"), py::arg("p_drop"), py::arg("causal") = false, py::kw_only(),
-          py::arg("cos") = py::none(), py::arg("sin") = py::none());
+          py::arg("cos") = py::none(), py::arg("sin") = py::none(), py::arg("window") = 0);
     m.def("rope_forward", &rope_forward,
           "rotary position embeddings (half-split convention, positions 0 .. S-1) on the query and key heads of qkv "
-          "[B, S, (heads + 2*kv_heads)*128] from f32 [S, 64] tables -> the rotated tensor in qkv's layout (value heads "
-          "copied)",
+          "[B, S, (heads + 2*kv_heads)*128], S 64..8192 in steps of 64, from f32 [S, 64] tables -> the rotated tensor in "
+          "qkv's layout (value heads copied)",
           py::arg("qkv"), py::arg("heads"), py::arg("kv_heads"), py::arg("cos"), py::arg("sin"));
     m.def("gemm_nt", &gemm_nt, py::arg("a"), py::arg("b"), py::arg("bias") = py::none(), py::arg("out") = py::none(),
           py::arg("accumulate") = false, py::arg("bn") = -1,

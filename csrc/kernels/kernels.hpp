@@ -533,18 +533,22 @@ void launch_attention_backward(const uint16_t *qkv, const uint16_t *out, const f
 // registers (one workgroup per K/V head and key block) and rounded once.
 // cos / sin (both or neither; f32 [S, 64] on the device): qkv holds heads that launch_rope_forward rotated, and the
 // backward's dQ and dK/dV epilogues apply the transposed rotation to dq and dk in f32 before their one rounding.
+// window (0: none; else a positive multiple of 64, causal only): query q attends to keys q - window < k <= q, the
+// band instantiations of the causal kernels, every S that is a multiple of 64 from 64 to kAttentionWindowMaxS; a window
+// of S or more is plain causal attention at those S.
+constexpr int kAttentionWindowMaxS = 8192;
 bool attention_d128_supported(int S);
-bool attention_gqa_supported(int S, int heads, int kv_heads);
+bool attention_gqa_supported(int S, int heads, int kv_heads, int window = 0);
 void launch_attention_gqa_forward(const uint16_t *qkv, uint16_t *out, float *lse, int B, int S, int H, int Hkv,
-                                  float scale, uint32_t seed, float p_drop, bool causal, hipStream_t s);
+                                  float scale, uint32_t seed, float p_drop, bool causal, hipStream_t s, int window = 0);
 void launch_attention_gqa_backward(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *dout,
                                    uint16_t *dqkv, float *dsum, int B, int S, int H, int Hkv, float scale,
                                    uint32_t seed, float p_drop, bool causal, hipStream_t s, const float *cos = nullptr,
-                                   const float *sin = nullptr);
+                                   const float *sin = nullptr, int window = 0);
 // Rotary position embeddings at head dim 128 (attention_rope.hip), half-split convention over the whole head,
 // positions 0 .. S - 1: out = qkv [B, S, (H + 2 Hkv) * 128] with the H query and Hkv key heads rotated by the f32
 // [S, 64] tables (x'[i] = x[i] cos - x[i + 64] sin, x'[i + 64] = x[i + 64] cos + x[i] sin, f32, rounded once) and the
-// value heads copied.  S, H, Hkv as attention_gqa_supported.
+// value heads copied.  H, Hkv as attention_gqa_supported, S as it allows with a window (to kAttentionWindowMaxS).
 void launch_rope_forward(const uint16_t *qkv, uint16_t *out, const float *cos, const float *sin, int B, int S, int H,
                          int Hkv, hipStream_t s);
 

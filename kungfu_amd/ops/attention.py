@@ -72,6 +72,21 @@ and dK/dV kernels, ahead of their single rounding to bf16, so the backward has n
 the (mask, S, G) triples of ``_ROPE_ROUTED_AWAY``) rotates Q and K in torch, which autograd differentiates, and runs
 ``self_attention`` on the result without ``rope``: every path above is reached that way.  A ``rope`` that is not
 positive and finite is a ``ValueError``; ``rope=None`` is the call without the keyword.
+
+Sliding-window (local) causal attention (Mistral): ``self_attention(..., causal=True, window=W)`` -- query ``q`` attends
+to keys ``q - W < k <= q``, at most ``W`` keys, itself included.  ``W`` is a positive multiple of 64.  At head dim 128,
+with or without ``kv_heads`` and ``rope``, the band instantiations of csrc/kernels/attention_d128.hip's causal kernels
+serve every S that is a multiple of 64 from 64 to 8192: query block ``i`` streams key blocks ``max(0, i - W/64) .. i``
+only, the block at the band's lower edge and the diagonal block are the two masked ones, and the dK/dV kernel streams
+the ``W/64 + 1`` query blocks that see its key block, so the work grows with ``S * W``, not ``S * S``
+(profiles/attention_window.md).  Same layouts, dropout hash, rope epilogues and bitwise reproducibility; multi-head
+attention runs them at one head per group.  ``W >= S`` is plain causal attention: for S <= 1024 it is the call without
+``window`` (bitwise), beyond that the band kernels compute it, which makes ``window=S`` the long-context causal call.
+``window`` without ``causal=True``, with ``lengths``, or not a positive multiple of 64 is a ``ValueError``;
+``window=None`` is the call without the keyword.  Every other call (CPU, f32, head dim 64, other S, S > 128 with
+``KUNGFU_ATTN_LONG=0``, ``_WINDOW_ENABLED = False``, ``rope`` with ``_ROPE_ENABLED = False``, the (S, W, G) triples of
+``_WINDOW_ROUTED_AWAY``) rotates in torch if ``rope`` is given, expands K/V over the group and runs
+``F.scaled_dot_product_attention`` with a boolean ``[S, S]`` band mask.
 """
 from __future__ import annotations
 
@@ -249,21 +264,21 @@ _ROPE_ROUTED_AWAY: frozenset = frozenset()
 _ROPE_ENABLED = True
 
 
-def _rope_attention(qkv: torch.Tensor, heads: int, p: float, lengths, causal: bool, kv_heads, rope) -> torch.Tensor:
-    """``self_attention`` with ``rope``: the fused rotation where the grouped-query kernels serve the call, else the
-    rotation in torch around ``self_attention`` without ``rope``."""
+def _check_rope(qkv: torch.Tensor, heads: int, kv_heads, rope) -> int:
+    """The ``ValueError``s of ``rope`` -> the number of K/V heads."""
     if isinstance(rope, bool) or not isinstance(rope, (int, float)) or not (0.0 < rope < math.inf):
         raise ValueError("self_attention: rope must be a positive finite base (for instance 10000.0), got %r" % (rope,))
     Hkv = heads if kv_heads is None else kv_heads
-    B, S, W = qkv.shape
+    W = qkv.shape[2]
     if Hkv < 1 or heads % Hkv or W % (2 * (heads + 2 * Hkv)):
         raise ValueError("self_attention: rope needs kv_heads to divide heads and qkv's last dim to be "
                          "(heads + 2*kv_heads) * dh with dh even, got %d for heads %d, kv_heads %d" % (W, heads, Hkv))
-    if (_ROPE_ENABLED and lengths is None and W == (heads + 2 * Hkv) * 128 and eligible_gqa(qkv, heads, Hkv, causal)
-            and (bool(causal), S, heads // Hkv) not in _ROPE_ROUTED_AWAY):
-        seed = int(torch.randint(0, 2**31 - 1, (1,)).item())  # CPU generator: no device sync
-        dropout_seed.base(qkv.device)
-        return _AttnRopeFn.apply(qkv, heads, Hkv, float(p), seed, bool(causal), float(rope))
+    return Hkv
+
+
+def _rope_in_torch(qkv: torch.Tensor, heads: int, Hkv: int, rope: float) -> torch.Tensor:
+    """``qkv`` with its Q and K heads rotated by torch operations, which autograd differentiates."""
+    B, S, W = qkv.shape
     dh = W // (heads + 2 * Hkv)
     cos, sin = (t[None, :, None, :] for t in rope_tables(S, rope, qkv.device, dh // 2))
     x = qkv.view(B, S, heads + 2 * Hkv, dh)
@@ -271,7 +286,94 @@ def _rope_attention(qkv: torch.Tensor, heads: int, p: float, lengths, causal: bo
     # in f32 (f64 for f64 inputs) with one rounding, as the kernel
     x1, x2 = qk.to(torch.promote_types(qkv.dtype, torch.float32)).split(dh // 2, dim=3)
     rot = torch.cat((x1 * cos - x2 * sin, x2 * cos + x1 * sin), dim=3).to(qkv.dtype)
-    return self_attention(torch.cat((rot, v), dim=2).view(B, S, W), heads, p, lengths, causal, kv_heads)
+    return torch.cat((rot, v), dim=2).view(B, S, W)
+
+
+def _rope_attention(qkv: torch.Tensor, heads: int, p: float, lengths, causal: bool, kv_heads, rope) -> torch.Tensor:
+    """``self_attention`` with ``rope``: the fused rotation where the grouped-query kernels serve the call, else the
+    rotation in torch around ``self_attention`` without ``rope``."""
+    Hkv = _check_rope(qkv, heads, kv_heads, rope)
+    B, S, W = qkv.shape
+    if (_ROPE_ENABLED and lengths is None and W == (heads + 2 * Hkv) * 128 and eligible_gqa(qkv, heads, Hkv, causal)
+            and (bool(causal), S, heads // Hkv) not in _ROPE_ROUTED_AWAY):
+        seed = int(torch.randint(0, 2**31 - 1, (1,)).item())  # CPU generator: no device sync
+        dropout_seed.base(qkv.device)
+        return _AttnRopeFn.apply(qkv, heads, Hkv, float(p), seed, bool(causal), float(rope))
+    return self_attention(_rope_in_torch(qkv, heads, Hkv, rope), heads, p, lengths, causal, kv_heads)
+
+
+class _AttnWindowFn(torch.autograd.Function):
+    """Sliding-window causal attention at head dim 128: the band instantiations of attention_d128.hip's causal kernels,
+    behind attention_rope.hip's rotation when ``base`` is given (then the backward's epilogues rotate dq and dk back)."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads, kv_heads, p, seed, window, base):
+        scale = 1.0 / math.sqrt(128.0)
+        cos, sin = (None, None) if base is None else rope_tables(qkv.shape[1], base, qkv.device)
+        rot = qkv if base is None else hip().rope_forward(qkv, heads, kv_heads, cos, sin)
+        out, lse = hip().attention_gqa_forward(rot, heads, kv_heads, scale, seed, p, True, window)
+        ctx.save_for_backward(rot, out, lse, cos, sin)  # (with base the unrotated qkv is not kept)
+        ctx.heads, ctx.kv_heads, ctx.p, ctx.seed, ctx.scale, ctx.window = heads, kv_heads, p, seed, scale, window
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        rot, out, lse, cos, sin = ctx.saved_tensors
+        dqkv = hip().attention_gqa_backward(rot, out, lse, dout.contiguous(), ctx.heads, ctx.kv_heads, ctx.scale,
+                                            ctx.seed, ctx.p, True, cos=cos, sin=sin, window=ctx.window)
+        return dqkv, None, None, None, None, None, None
+
+
+# (S, W, G) triples whose forward + backward on the band kernels did not beat the SDPA band-mask fallback by more than
+# the measured spread (profiles/attention_window.md): they keep the fallback
+_WINDOW_ROUTED_AWAY: frozenset = frozenset()
+# False: every window call keeps its fallback (tests and tools/bench_attention.py compare the paths in one process)
+_WINDOW_ENABLED = True
+
+
+def eligible_window(qkv: torch.Tensor, heads: int, kv_heads: int, window: int) -> bool:
+    """Whether the band kernels serve this causal call: head dim 128, bf16, contiguous, on the GPU, S a multiple of 64
+    up to 8192 that the measurements did not route away; ``KUNGFU_ATTN_LONG=0`` keeps S > 128 off them."""
+    return (_WINDOW_ENABLED and qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.dim() == 3 and qkv.is_contiguous()
+            and qkv.shape[2] == (heads + 2 * kv_heads) * 128 and qkv.shape[1] <= 8192
+            and (_LONG_ENABLED or qkv.shape[1] <= 128)
+            and (int(qkv.shape[1]), int(window), heads // kv_heads) not in _WINDOW_ROUTED_AWAY
+            and hip_available() and hip().attention_gqa_supported(int(qkv.shape[1]), heads, kv_heads, int(window)))
+
+
+def _window_attention(qkv: torch.Tensor, heads: int, p: float, lengths, causal: bool, kv_heads, rope,
+                      window) -> torch.Tensor:
+    """``self_attention`` with ``window``: the band kernels, else the rotation in torch (with ``rope``), K/V expanded
+    over the group and SDPA with a boolean band mask."""
+    if isinstance(window, bool) or not isinstance(window, int) or window <= 0 or window % 64:
+        raise ValueError("self_attention: window must be a positive multiple of 64, got %r" % (window,))
+    if not causal:
+        raise ValueError("self_attention: window needs causal=True (query q attends to keys q - window < k <= q)")
+    if lengths is not None:
+        raise ValueError("self_attention: window takes no lengths")
+    B, S, W = qkv.shape
+    if window >= S and S <= 1024:  # plain causal attention on today's paths
+        return self_attention(qkv, heads, p, None, True, kv_heads, rope)
+    Hkv = heads if kv_heads is None else kv_heads
+    if rope is not None:
+        _check_rope(qkv, heads, kv_heads, rope)
+    if Hkv < 1 or heads % Hkv or W % (heads + 2 * Hkv):
+        raise ValueError("self_attention: kv_heads must divide heads and qkv's last dim must be (heads + 2*kv_heads) "
+                         "* dh, got %d for heads %d, kv_heads %d" % (W, heads, Hkv))
+    if eligible_window(qkv, heads, Hkv, window) and (rope is None or _ROPE_ENABLED):
+        seed = int(torch.randint(0, 2**31 - 1, (1,)).item())  # CPU generator: no device sync
+        dropout_seed.base(qkv.device)
+        return _AttnWindowFn.apply(qkv, heads, Hkv, float(p), seed, int(window), None if rope is None else float(rope))
+    if rope is not None:
+        qkv = _rope_in_torch(qkv, heads, Hkv, rope)
+    dh, G = W // (heads + 2 * Hkv), heads // Hkv
+    q, k, v = qkv.split((heads * dh, Hkv * dh, Hkv * dh), dim=2)
+    q = q.view(B, S, heads, dh).transpose(1, 2)
+    k, v = (t.view(B, S, Hkv, dh).transpose(1, 2).repeat_interleave(G, dim=1) for t in (k, v))
+    pos = torch.arange(S, device=qkv.device)
+    band = (pos[None, :] <= pos[:, None]) & (pos[None, :] > pos[:, None] - window)  # [query, key]
+    a = F.scaled_dot_product_attention(q, k, v, attn_mask=band, dropout_p=p)
+    return a.transpose(1, 2).reshape(B, S, heads * dh)
 
 
 def eligible(qkv: torch.Tensor, heads: int, lengths=None, causal: bool = False) -> bool:
@@ -312,13 +414,16 @@ def _lengths_fallback(qkv: torch.Tensor, heads: int, p: float, lengths: torch.Te
 
 
 def self_attention(qkv: torch.Tensor, heads: int, p: float = 0.0, lengths: torch.Tensor | None = None,
-                   causal: bool = False, kv_heads: int | None = None, rope: float | None = None) -> torch.Tensor:
+                   causal: bool = False, kv_heads: int | None = None, rope: float | None = None,
+                   window: int | None = None) -> torch.Tensor:
     """softmax(Q K^T / sqrt(dh)) V with dropout ``p`` on the probabilities, per head (dh = 64 or 128 fused);
     ``qkv``: [B, S, 3*H*dh] -> [B, S, H*dh].  ``lengths`` (int32 [B], on qkv's device): the valid
     tokens of each padded sequence; ``causal``: query q attends to keys <= q; ``kv_heads``: grouped-query heads,
-    ``qkv`` [B, S, (H + 2*kv_heads)*dh]; ``rope``: the base of rotary position embeddings on Q and K (module
-    docstring)."""
+    ``qkv`` [B, S, (H + 2*kv_heads)*dh]; ``rope``: the base of rotary position embeddings on Q and K; ``window``:
+    with ``causal``, only the keys q - window < k <= q (module docstring)."""
     B, S, D3 = qkv.shape
+    if window is not None:
+        return _window_attention(qkv, heads, p, lengths, causal, kv_heads, rope, window)
     if causal and lengths is not None:
         raise ValueError("self_attention: causal attention takes no lengths: right padding cannot reach a valid row")
     if rope is not None:
@@ -353,12 +458,13 @@ def self_attention(qkv: torch.Tensor, heads: int, p: float = 0.0, lengths: torch
     return a.transpose(1, 2).reshape(B, S, heads * dh)
 
 
-def dropout_keep(seed: int, B: int, H: int, S: int, p: float, device=None) -> torch.Tensor:
-    """The kernels' keep mask [B, H, S(query), S(key)] (bool), computed with torch int64 ops."""
+def dropout_keep(seed: int, B: int, H: int, S: int, p: float, device=None, start: int = 0) -> torch.Tensor:
+    """The kernels' keep mask [B, H, S(query), S(key)] (bool), computed with torch int64 ops; ``start``: of the queries
+    and keys ``start .. start + S - 1`` of a longer sequence."""
     m32 = 0xFFFFFFFF
     bh = torch.arange(B * H, device=device, dtype=torch.int64).view(B * H, 1, 1)
-    q = torch.arange(S, device=device, dtype=torch.int64).view(1, S, 1)
-    k = torch.arange(S, device=device, dtype=torch.int64).view(1, 1, S)
+    q = torch.arange(start, start + S, device=device, dtype=torch.int64).view(1, S, 1)
+    k = torch.arange(start, start + S, device=device, dtype=torch.int64).view(1, 1, S)
     x = ((q << 16) | k) ^ seed
     x = (x * 0x9E3779B1) & m32
     x = x ^ (((bh * 0x85EBCA77) & m32) + (x >> 15)) & m32

@@ -28,8 +28,12 @@ With ``--head-dim 128 --rope BASE`` (with or without ``--kv-heads``) it times ``
 the fused rotation (attention_rope.hip and the head dim 128 backward's epilogues) against the rotation in torch
 around the fused kernels and around SDPA, and the rotation kernel alone.
 
+With ``--head-dim 128 --window W`` (with or without ``--kv-heads``) it times ``self_attention(..., causal=True,
+window=W)``: the band kernels of attention_d128.hip against the SDPA band-mask fallback and, at S <= 1024, the full
+causal kernels, with the predicted ratio of block steps.
+
     python tools/bench_attention.py [calls] [--batch 128] [--seq 128] [--heads 12] [--lengths 0.5|random] [--causal]
-                                    [--head-dim 64|128] [--kv-heads N] [--rope BASE]"""
+                                    [--head-dim 64|128] [--kv-heads N] [--rope BASE] [--window W]"""
 import argparse
 import os
 import sys
@@ -322,6 +326,55 @@ def rope(args, H):
         tag, t, rs[0], rs[-1], nbytes / t / 1e6, nbytes, 100 * nbytes / 5.3e6 / t), flush=True)
 
 
+def window(args, H):
+    """Sliding-window causal attention at head dim 128 (``--window W``, with or without ``--kv-heads``): forward and
+    backward time of ``self_attention(..., causal=True, window=W)`` on the band kernels (twice per round: ``band
+    again`` / ``band`` is the run-to-run spread), on its SDPA band-mask fallback (``_WINDOW_ENABLED = False``) and,
+    where S <= 1024, of the full causal kernels at the same shape, next to the predicted ratio of block steps
+    sum over qb of (min(qb, w) + 1) against n (n + 1) / 2.  The variants alternate over the rounds."""
+    B, S, NH, W = args.batch, args.seq, args.heads, args.window
+    NKV = NH if args.kv_heads is None else args.kv_heads
+    G, kv, n, w = NH // NKV, args.kv_heads, S // 64, W // 64
+    torch.manual_seed(0)
+    qkv = (torch.randn(B, S, (NH + 2 * NKV) * 128, device="cuda") * 0.5).bfloat16()
+    dout = (torch.randn(B, S, NH * 128, device="cuda") * 0.1).bfloat16()
+    steps = sum(min(qb, w) + 1 for qb in range(n)) / (n * (n + 1) / 2)
+    tag = "S=%d W=%d B=%d G=%d" % (S, W, B, G)
+
+    def route(enabled, q, p, win):
+        attn._WINDOW_ENABLED = enabled
+        try:
+            return attn.self_attention(q, NH, p, causal=True, kv_heads=kv, window=win)
+        finally:
+            attn._WINDOW_ENABLED = True
+
+    for p in (0.1, 0.0):
+        variants = {}
+        for name, enabled, win in (("band", True, W), ("sdpa mask", False, W)) + ((("causal", True, None),) if S <= 1024 else ()):
+            q = qkv.clone().requires_grad_(True)
+            y = route(enabled, q, p, win)
+            assert (type(y.grad_fn).__name__ == "_AttnWindowFnBackward") == (name == "band"), (name, y.grad_fn)
+            variants[name] = (lambda enabled=enabled, q=q, win=win: route(enabled, q, p, win),
+                              lambda y=y, q=q: torch.autograd.grad(y, q, dout, retain_graph=True))
+        variants = {"band": variants["band"], "band again": variants["band"],
+                    **{k: v for k, v in variants.items() if k != "band"}}
+        ts = {k: [] for k in variants}
+        for _ in range(args.rounds):
+            for k, (f, b) in variants.items():
+                ts[k].append((med(f, args.calls), med(b, args.calls)))
+        m = {}
+        for k, v in ts.items():
+            fs, bs, tot = sorted(f for f, _ in v), sorted(b for _, b in v), sorted(f + b for f, b in v)
+            m[k] = tot[len(tot) // 2]
+            print("%s p=%.1f  %-10s fwd %8.1f us  bwd %8.1f us  fwd+bwd %8.1f us (min %8.1f max %8.1f) over %d rounds" % (
+                tag, p, k, fs[len(fs) // 2], bs[len(bs) // 2], m[k], tot[0], tot[-1], len(v)), flush=True)
+        line = "%s p=%.1f  fwd+bwd: band / sdpa mask %.3f   band again / band %.3f" % (
+            tag, p, m["band"] / m["sdpa mask"], m["band again"] / m["band"])
+        if "causal" in m:
+            line += "   band / causal %.3f (block steps %.3f)" % (m["band"] / m["causal"], steps)
+        print(line, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("calls", nargs="?", type=int, default=20, help="calls to time")
@@ -340,10 +393,21 @@ def main():
     ap.add_argument("--rope", type=float, default=None, metavar="BASE",
                     help="rotary position embeddings of this base (needs --head-dim 128, with or without --kv-heads): "
                          "the fused rotation against the rotation in torch around the fused kernels and around SDPA")
+    ap.add_argument("--window", type=int, default=None, metavar="W",
+                    help="sliding-window causal attention over W keys (needs --head-dim 128, with or without "
+                         "--kv-heads): the band kernels against the SDPA band-mask fallback and, at S <= 1024, the full "
+                         "causal kernels")
     args = ap.parse_args()
     n = args.calls
     H = hip()
     B, S, NH = args.batch, args.seq, args.heads
+    if args.window is not None:
+        if args.head_dim != 128 or (args.kv_heads is not None and (args.kv_heads < 1 or NH % args.kv_heads)):
+            ap.error("--window needs --head-dim 128 and, if given, --kv-heads a divisor of --heads")
+        if args.window >= S and S <= 1024:
+            ap.error("--window >= --seq <= 1024 is the causal call: nothing to compare")
+        print("B=%d S=%d H=%d Hkv=%s window=%d" % (B, S, NH, args.kv_heads, args.window), flush=True)
+        return window(args, H)
     if args.rope is not None:
         if args.head_dim != 128 or (args.kv_heads is not None and (args.kv_heads < 1 or NH % args.kv_heads)):
             ap.error("--rope needs --head-dim 128 and, if given, --kv-heads a divisor of --heads")
